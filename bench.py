@@ -23,10 +23,18 @@ so the group only carries the barriers around the timed region and the per-rank 
 reduction -- the same code path with or without a GPU.  `--dry-run` replaces the HIP work
 with a CPU stand-in (tests the launcher and the aggregation on a machine without a GPU).
 
-Legs besides the device-resident steps (rank 0 unless noted): the PCIe-inclusive rate from
-pinned host memory (every rank at once, `--pcie`, default on), the per-call latency of the
-drop-in entry points, and the reference CPU codec on the host cores (`cpu_baseline`) over
-the same erasure patterns as the GPU workload.
+A plain run sets up, settles and warms up, times exactly `--steps` steps, checks that the
+decode restored the data, and prints the line.  `--dump-outputs DIR` also writes what the last
+timed step left its caller (dump_outputs) as DIR/<name>.npy; the workload is seeded, so the
+same arguments give the same inputs in every run and two builds compare output for output.
+
+`--full` adds the legs that take runs of their own, after the timed region (rank 0 unless
+noted): the step through the pointer-table calls (`--ptr`), on the block-size family modules
+and on the reference benchmark's block order (`--family`), the PCIe-inclusive rate from
+pinned host memory (every rank at once, `--pcie`), the per-call latency of the drop-in entry
+points (`--dropin-calls`), and the reference CPU codec on the host cores (`--cpu-baseline`)
+over the same erasure patterns as the GPU workload.  Each is on under `--full` unless its own
+option turns it off.
 
 Prints one JSON line (rank 0).  See DESIGN.md for the roofline and cpu_baseline definitions.
 """
@@ -79,6 +87,13 @@ def parse(argv=None):
     ap.add_argument("--stripes", type=int, default=0, help="override stripes per GPU (weak scaling)")
     ap.add_argument("--global-stripes", type=int, default=0,
                     help="strong scaling: total stripes split over the ranks with shard_range")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the legs with runs of their own: pointer tables, "
+                         "family modules, reference block order, PCIe, drop-in latency, CPU baseline "
+                         "(the options below choose among them; without --full none of them runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32; a fixed seeded "
+                         "sample of stripes and byte columns, under 64 MB in all)")
     ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "off"])
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="wall-time budget of the CPU baseline leg")
     ap.add_argument("--dropin-calls", type=int, default=-1,
@@ -758,6 +773,38 @@ def reflayout_leg(lh, k, m, nbytes, X, rows0, reps=5, settle_s=0.25):
                     f"mean of {reps} after {warm} untimed passes"}
 
 
+DUMP_ELEMS = 12 << 20   # float32 elements per dump: 48 MB, under the 64 MB allowed
+
+
+def dump_outputs(path, rank, k, m, nbytes, arrays):
+    """--dump-outputs: what the last timed step left its caller, as <path>/<name>.npy in float32
+    (rank r > 0: <name>.rank<r>.npy).  `arrays` maps a name to a tensor or array whose first
+    dimension is the stripe and whose last, where it is 3-d, the byte within a block.  Large
+    outputs are sampled: the same stripes and byte columns of every array, drawn from a fixed
+    seed (so two runs with the same arguments dump the same elements), all of them when they
+    fit; `stripe_index` and `byte_index` record which."""
+    import numpy as np
+    stripes = next(iter(arrays.values())).shape[0]
+    rng = np.random.Generator(np.random.PCG64(20240229))
+    cols = np.sort(rng.choice(nbytes, size=min(nbytes, 4096), replace=False))
+    per_stripe = (k + m) * len(cols) + k + 1
+    sel = np.sort(rng.choice(stripes, size=max(1, min(stripes, DUMP_ELEMS // per_stripe)), replace=False))
+    os.makedirs(path, exist_ok=True)
+    suffix = f".rank{rank}" if rank else ""
+    out = {"stripe_index": sel, "byte_index": cols}
+    for name, a in arrays.items():
+        if hasattr(a, "data_ptr"):   # a tensor: sample on its device, copy the sample
+            import torch
+            a = a[torch.from_numpy(sel).to(a.device)]
+            a = a[..., torch.from_numpy(cols).to(a.device)] if a.dim() == 3 else a
+            out[name] = a.cpu().numpy()
+        else:
+            a = np.asarray(a)[sel]
+            out[name] = a[..., cols] if a.ndim == 3 else a
+    for name, a in out.items():
+        np.save(os.path.join(path, name + suffix + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def load_profile(name):
     path = os.path.join(REPO, "profiles", name)
     return json.load(open(path)) if os.path.exists(path) else None
@@ -810,6 +857,7 @@ def main():
         rows = rows0.clone()
         stream = torch.cuda.current_stream()  # every kernel below is launched on this stream
         traces = {}
+        last = {}   # the status tensor the last step's decode returned
 
         def step(ev=None):
             if ev is not None:
@@ -823,7 +871,7 @@ def main():
             rows.copy_(rows0)
             if ev is not None:
                 ev[2].record(stream)
-            lh.decode_batch(D, rows, m, stream=stream)
+            last["status"] = lh.decode_batch(D, rows, m, stream=stream)
             traces.setdefault("decode", lh.last_launch())
             if ev is not None:
                 ev[3].record(stream)
@@ -868,6 +916,18 @@ def main():
         restored = torch.gather(D, 1, order.unsqueeze(-1).expand(-1, -1, nbytes))
         assert torch.equal(restored, X), "decode did not restore the data"
         del restored, order
+    if args.dump_outputs:
+        if dry:
+            dump_outputs(args.dump_outputs, rank, k, m, nbytes, {"standin": out_buf})
+        else:
+            # The decode works in place: with erasures="max" it has overwritten the recovery
+            # blocks the encode wrote into D's recovery slots, so the same encode call runs
+            # once more here, untimed, into a buffer of its own.
+            rec = R if rec_index is not None else lh.encode_batch(X, m, stream=stream)
+            dump_outputs(args.dump_outputs, rank, k, m, nbytes,
+                         {"recovery": rec, "decoded_blocks": D, "decoded_rows": rows,
+                          "decode_status": last["status"]})
+            del rec
     elapsed_ranks = per_rank(world, rank, t1 - t0, dry)
     stripes_ranks = per_rank(world, rank, stripes, dry)
     elapsed = max(elapsed_ranks)
@@ -971,20 +1031,21 @@ def main():
                     "frac_of_measured_floor": round(FLAT_FLOOR_MS / enc_ms, 4),
                     "floor_frac_of_hbm_peak": round(k * nbytes * stripes / (FLAT_FLOOR_MS * 1e-3) / 1e9
                                                     / HBM_PEAK_GBS, 4)})
-    if not dry and args.ptr == "on":
+    legs = args.full and not dry   # everything below: runs of their own, --full only
+    if legs and args.ptr == "on":
         out["ptr_tables"] = ptr_leg(lh, k, m, nbytes, X, D, rows0, rec_view, rec_index)
-    if not dry and rank == 0 and args.family == "on" and rec_index is None:
+    if legs and rank == 0 and args.family == "on" and rec_index is None:
         out["reference_order"] = reflayout_leg(lh, k, m, nbytes, X, rows0)
         fam = family_leg(lh, k, m, nbytes, X, D, rows0, rec_view)
         if fam is not None:
             out["family"] = fam
-    if not dry and args.pcie == "on":
+    if legs and args.pcie == "on":
         # every rank at once: the node's host links and memory are shared
         out["pcie"] = pcie_leg(lh, args, k, m, nbytes, X, D, rows0, rec_view, rec_index, world, rank)
     if args.share_gpu and world > 1:
         out["share_gpu"] = (f"{world} ranks on {torch.cuda.device_count() if not dry else 0} device(s): a functional "
                             "check of the N > 1 control path, not a scaling measurement")
-    if rank == 0 and not dry:
+    if legs and rank == 0:
         calls = args.dropin_calls if args.dropin_calls >= 0 else max(10, min(2000, int(4e7 / (k * nbytes))))
         if calls:
             out["dropin_per_call"] = dropin_leg(lh, k, m, nbytes, calls)

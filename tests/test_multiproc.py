@@ -119,6 +119,51 @@ def test_bench_rejects_world_mismatch():
     assert r.returncode != 0 and "WORLD_SIZE=1" in r.stderr
 
 
+def test_bench_dump_outputs_and_full_options(tmp_path):
+    """`--dump-outputs DIR` writes float32 .npy files after the timed steps, and `--full` is
+    accepted (dry run: the CPU stand-in's output; the extra legs need a GPU and stay off)."""
+    import numpy as np
+    r, line = _bench("--gpus", "1", "--dry-run", "--steps", "2", "--warmup", "1", "--full",
+                     "--dump-outputs", str(tmp_path / "out"))
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    assert sorted(os.listdir(tmp_path / "out")) == ["byte_index.npy", "standin.npy", "stripe_index.npy"]
+    got = np.load(tmp_path / "out" / "standin.npy")
+    assert got.dtype == np.float32 and not got.any()   # x ^ x
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """bench.dump_outputs: the same seeded stripes and byte columns of every array in every
+    call, float32 values equal to the bytes, under 64 MB in all for the largest config."""
+    import bench
+    import numpy as np
+    import torch
+    k, m, nbytes, stripes = 200, 56, 65536, 64           # CONFIGS["k200m56"]
+    # one block of memory expanded to [stripes, k, bytes]: byte c of every block is c % 251
+    rows = torch.arange(stripes * k, dtype=torch.int64).reshape(stripes, k).to(torch.uint8)
+    blocks = (torch.arange(nbytes, dtype=torch.int64) % 251).to(torch.uint8).expand(stripes, k, nbytes)
+    rec = blocks[:, :m]
+    arrays = {"recovery": rec, "decoded_blocks": blocks, "decoded_rows": rows,
+              "decode_status": np.zeros(stripes, dtype=np.int8)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), 0, k, m, nbytes, arrays)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(n + ".npy" for n in list(arrays) + ["stripe_index", "byte_index"])
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    for f in files:
+        assert a[f[:-4]].dtype == np.float32
+        assert np.array_equal(a[f[:-4]], np.load(tmp_path / "b" / f))
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    sel, cols = a["stripe_index"].astype(int), a["byte_index"].astype(int)
+    assert len(set(sel)) == len(sel) and len(set(cols)) == len(cols) == 4096
+    assert a["decoded_blocks"].shape == (len(sel), k, 4096) and a["recovery"].shape == (len(sel), m, 4096)
+    assert np.array_equal(a["decoded_blocks"][3, 7], cols % 251)
+    assert np.array_equal(a["decoded_rows"], rows.numpy()[sel].astype(np.float32))
+    # rank r > 0 writes beside rank 0's files
+    bench.dump_outputs(str(tmp_path / "a"), 1, k, m, nbytes, {"decode_status": arrays["decode_status"]})
+    assert os.path.exists(tmp_path / "a" / "decode_status.rank1.npy")
+
+
 def test_cpu_baseline_uses_the_workload_patterns():
     """bench.py's cpu_baseline decodes the GPU workload's own erasure patterns (per-stripe e
     and recovery rows from the Block.row bytes), so its sample states the same mean e."""

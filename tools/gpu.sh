@@ -9,7 +9,7 @@
 #   tests:EXPR       pytest -m gpu -k EXPR
 #   testscheck[:EXPR] pytest -m gpu -k EXPR (default phase_b) on the phase-B checked build
 #   smoke            __graft_entry__.smoke()
-#   bench[:CFG]      bench.py (default k29m4; k128m32 / k200m56 with 5 steps)
+#   bench[:CFG]      bench.py --full (default k29m4; k128m32 / k200m56 with 5 steps)
 #   prof[:CFG]       rocprofv3 --kernel-trace --stats of a short bench run
 #   pmc[:CFG]        FETCH_SIZE and WRITE_SIZE passes (separate runs) + tools/pmc_summary.py
 #   sq[:CFG]         one SQ counter pass (waves, cycles, waits, VALU/VMEM issue)
@@ -17,8 +17,8 @@
 #   ubench:NAME[:G]  tools/NAME (built here beforehand) with optional group list G (commas)
 #   stress[:SECONDS]  tools/stress.py: random shapes, strided and pointer-table calls vs the oracle
 #   tune:VARIANTS[@k m bytes stripes]  tools/tune.py with TUNE_VARIANTS=VARIANTS (env TUNE_ROUNDS)
-#   bench2           bench.py --gpus 2 --share-gpu (the N>1 control path on one GPU)
-#   benchg[:CFG]     bench.py on the generic kernels only (LONGHAIR_AMD_PATH=generic), 5 steps
+#   bench2           bench.py --full --gpus 2 --share-gpu (the N>1 control path on one GPU)
+#   benchg[:CFG]     bench.py --full on the generic kernels only (LONGHAIR_AMD_PATH=generic), 5 steps
 set -o pipefail
 cd "$(dirname "$0")/.."
 OUT=gpurun_out/${1:?usage: tools/gpu.sh OUT STEP...}
@@ -50,18 +50,18 @@ for step in "$@"; do
       cfg=${arg:-k29m4}
       extra=()
       [ "$cfg" != k29m4 ] && extra=(--steps 5 --warmup 2)
-      timeout -k 10 400 python bench.py --config "$cfg" "${extra[@]}" > "$OUT/bench_$cfg.json" 2> "$OUT/bench_$cfg.err" || fail "$step" "$OUT/bench_$cfg.err"
+      timeout -k 10 400 python bench.py --full --config "$cfg" "${extra[@]}" > "$OUT/bench_$cfg.json" 2> "$OUT/bench_$cfg.err" || fail "$step" "$OUT/bench_$cfg.err"
       cat "$OUT/bench_$cfg.json" ;;
     benchg)
       cfg=${arg:-k29m4}
-      LONGHAIR_AMD_PATH=generic timeout -k 10 400 python bench.py --config "$cfg" --steps 5 --warmup 2 --cpu-baseline off --pcie off --dropin-calls 0 > "$OUT/benchg_$cfg.json" 2> "$OUT/benchg_$cfg.err" || fail "$step" "$OUT/benchg_$cfg.err"
+      LONGHAIR_AMD_PATH=generic timeout -k 10 400 python bench.py --full --config "$cfg" --steps 5 --warmup 2 --cpu-baseline off --pcie off --dropin-calls 0 > "$OUT/benchg_$cfg.json" 2> "$OUT/benchg_$cfg.err" || fail "$step" "$OUT/benchg_$cfg.err"
       cat "$OUT/benchg_$cfg.json" ;;
     bench2)
-      timeout -k 10 600 python bench.py --gpus 2 --share-gpu --steps 10 --warmup 2 > "$OUT/bench_gpus2.json" 2> "$OUT/bench_gpus2.err" || fail "$step" "$OUT/bench_gpus2.err"
+      timeout -k 10 600 python bench.py --full --gpus 2 --share-gpu --steps 10 --warmup 2 > "$OUT/bench_gpus2.json" 2> "$OUT/bench_gpus2.err" || fail "$step" "$OUT/bench_gpus2.err"
       cat "$OUT/bench_gpus2.json" ;;
     prof)
       cfg=${arg:-k29m4}
-      timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_$cfg" -o run --output-format csv -- python3 bench.py --config "$cfg" --steps 5 --warmup 2 --cpu-baseline off --pcie off --dropin-calls 0 > "$OUT/prof_$cfg.log" 2>&1 || fail "$step" "$OUT/prof_$cfg.log"
+      timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_$cfg" -o run --output-format csv -- python3 bench.py --full --config "$cfg" --steps 5 --warmup 2 --cpu-baseline off --pcie off --dropin-calls 0 > "$OUT/prof_$cfg.log" 2>&1 || fail "$step" "$OUT/prof_$cfg.log"
       find "$OUT/prof_$cfg" -name "*kernel_stats.csv" -exec cp {} "$OUT/${cfg}_kernel_stats.csv" \;
       grep -E "lh_" "$OUT/${cfg}_kernel_stats.csv" | cut -c1-160 ;;
     pmc)
