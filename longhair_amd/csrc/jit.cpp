@@ -143,18 +143,14 @@ static bool config_impl(int k, int m, int bytes, bool decode, JitConfig *cfg, bo
         const size_t at = cfg->defines.find(name);
         return at == std::string::npos ? dflt : std::atoi(cfg->defines.c_str() + at + std::strlen(name));
     };
-    // The fused decode's memory-order form (jit_codec.hip LH_DMO) streams slots in the same
-    // multi-slot steps.
-    const bool dmo = decode && cfg->lds && !cfg->plain && knob("LH_DMO=", 0) == 1;
+    // A decode module always streams one column per step (cps = 1).
     cfg->cps = 1;
-    if ((!decode || dmo) && cfg->lds) cfg->cps = std::max(1, std::min(5, k / 2));
+    if (!decode && cfg->lds) cfg->cps = std::max(1, std::min(5, k / 2));
     cfg->cps = knob("LH_CPS=", cfg->cps);
-    if (cfg->cps > 1 && !((!decode || dmo) && cfg->lds && k >= 2 * cfg->cps)) cfg->cps = 1;
+    if (cfg->cps > 1 && !(!decode && cfg->lds && k >= 2 * cfg->cps)) cfg->cps = 1;
     cfg->wgcu = knob("LH_WGCU=", cfg->cps > 1 ? 1 : 0);
     const int wpb = knob("LH_WPB=", 4);
     cfg->enc_wpb = (cfg->cps > 1 && wpb >= 1 && wpb <= 8) ? wpb : 4;
-    const int dwpb = knob("LH_DWPB=", 4);
-    cfg->dec_wpb = (decode && !cfg->plain && dwpb >= 1 && dwpb <= 8) ? dwpb : 4;
     // Block-size family (jit_codec.hip LH_FAMILY): the multi-column-step encode with the block
     // size a kernel argument, keyed by (k, m) alone.
     cfg->family = 0;

@@ -210,17 +210,9 @@ template <int X, int... I>
 __device__ __forceinline__ void lh_col_net(lh_word (&acc)[LH_M][8], const lh_word (&d)[8], lh_iseq<int, I...>) {
     (lh_net<LH_BM[I / 8][X][I % 8]>(acc[I / 8][I % 8], d), ...);
 }
-#ifndef LH_PROBE_LIGHT
-#define LH_PROBE_LIGHT 0  // (probe, wrong bytes: one XOR per sub-row of row 0 instead of the network)
-#endif
 template <int X>
 __device__ __forceinline__ void lh_column(lh_word (&acc)[LH_M][8], const lh_word (&d)[8]) {
-#if LH_PROBE_LIGHT
-#pragma unroll
-    for (int y = 0; y < 8; ++y) lh_xor(acc[0][y], d[(y + X) & 7]);
-#else
     lh_col_net<X>(acc, d, __make_integer_seq<lh_iseq, int, LH_M * 8>{});
-#endif
 }
 
 struct lh_lane {
@@ -277,18 +269,14 @@ __device__ __forceinline__ long long lh_block_id() {
 #endif
 }
 
-// The wave's index in its workgroup, wave-uniform to the compiler (LH_UNIWID): the per-wave LDS
+// The wave's index in its workgroup, wave-uniform to the compiler: the encode's per-wave LDS
 // rings indexed by it then have their addresses -- the LDS-DMAs' M0 -- in SGPRs.  With
 // threadIdx.x >> 6 the compiler treats the index as per-lane, keeps every ring slot / chunk
-// address in a VGPR (16 in the k29/m4 decode) and reads one back with v_readfirstlane before
-// each DMA.
-#ifndef LH_UNIWID
-#define LH_UNIWID 1
-#endif
-template <int ROLE>  // (LH_UNIWID bit 0: the encode's rings, bit 1: the decode's)
+// address in a VGPR and reads one back with v_readfirstlane before each DMA.  (The
+// size-specialised decode measured 0.4 % slower with the uniform index and keeps
+// threadIdx.x >> 6: profiles/r10h_tune_k29m4_uniwid.txt.)
 __device__ __forceinline__ int lh_wid() {
-    if constexpr ((LH_UNIWID >> ROLE) & 1) return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    return (int)(threadIdx.x >> 6);
+    return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 }
 
 #define LH_WAVE_LOOP(stripes)                                                                   \
@@ -573,33 +561,16 @@ __device__ __forceinline__ void lh_lds_put(unsigned char *p, const lh_word &w) {
 // advanced by x * bytes (profiles/r7q_tune_k29m4_erows.txt; found because the pointer-table
 // form ran faster, r7n_seq_probe_ptr.txt; padding the ring to the same LDS size: no change).
 // One 16-byte-per-lane LDS-DMA (global_load_lds_dwordx4): `lds` the wave-uniform LDS address
-// of lane 0's 16 bytes.
-// Round 6 found that with the builtin, hipcc's waitcnt pass cannot tell a ring slot being read
-// from the slots being filled (one __shared__ array) and puts s_waitcnt vmcnt(0) before every
-// column's first LDS read: the "4-slot ring" of the one-column kernels ran one column per wave
-// at a time.  Issued from inline asm (LH_ASM_DMA=1) the compiler sees no LDS write in flight
-// and the kernels' own counted waits (lh_wait_vmcnt) order the landing, so the ring really
-// runs 3 columns deep -- and measured SLOWER: encode 0.533 against 0.501 ms, decode 0.566
-// against 0.554 (ring depth 2 / 3: 0.562 / 0.557; profiles/r9a_tune_k29m4_asm_dma.txt).  The
-// HBM stream of this access pattern prefers fewer, longer runs in flight over deeper
-// prefetch (tools/ubench_r6.hip), which the multi-column steps below turn into a design:
-// they issue their DMAs from asm (lh_dma16_bufs) with one step in flight by construction.
-// The builtin (with its drain) stays the default of the one-column kernels.
-#ifndef LH_ASM_DMA
-#define LH_ASM_DMA 0
-#endif
+// of lane 0's 16 bytes.  With the builtin, hipcc's waitcnt pass cannot tell a ring slot being
+// read from the slots being filled (one __shared__ array) and puts s_waitcnt vmcnt(0) before
+// every column's first LDS read: the one-column kernels' ring runs one column per wave at a
+// time.  That drain is kept: the ring really running 3 columns deep (the DMAs issued from
+// inline asm) measured slower; the multi-column steps below issue theirs from
+// asm (lh_dma16_bufs) with one step in flight by construction.
 template <int NT>
 __device__ __forceinline__ void lh_dma16(const void *src, const void *lds) {
-#if LH_ASM_DMA
-    const unsigned m = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)lds);
-    if constexpr (NT)
-        asm volatile("global_load_lds_dwordx4 %0, off nt" ::"v"(src), "{m0}"(m) : "memory");
-    else
-        asm volatile("global_load_lds_dwordx4 %0, off" ::"v"(src), "{m0}"(m) : "memory");
-#else
     __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void *)src,
                                      (__attribute__((address_space(3))) void *)lds, 16, 0, NT ? 2 : 0);
-#endif
 }
 #define LH_LPR (LH_K + LH_M)
 struct lh_ldsrc {
@@ -635,32 +606,13 @@ __device__ __forceinline__ lh_u32x4r lh_rsrc(const void *base, unsigned bytes) {
     r.w = 0x00020000u;
     return r;
 }
-template <int NT>
-__device__ __forceinline__ void lh_dma16_buf(const lh_u32x4r &rs, int voff, const void *lds) {
-    const unsigned m = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)lds);
-    if constexpr (NT)
-        asm volatile("buffer_load_dwordx4 %0, %1, 0 offen nt lds" ::"v"(voff), "s"(rs), "{m0}"(m) : "memory");
-    else
-        asm volatile("buffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(voff), "s"(rs), "{m0}"(m) : "memory");
-}
-// ... with a wave-uniform byte offset `soff` added (SGPR soffset).
-#ifndef LH_CPS_POLI
-#define LH_CPS_POLI 0  // cache policy of the multi-column-step DMAs: 0 nt, 1 sc1 nt, 2 sc0 nt, 3 sc0 sc1 nt
-#endif
-#if LH_CPS_POLI == 1
-#define LH_CPS_POL "sc1 nt"
-#elif LH_CPS_POLI == 2
-#define LH_CPS_POL "sc0 nt"
-#elif LH_CPS_POLI == 3
-#define LH_CPS_POL "sc0 sc1 nt"
-#else
-#define LH_CPS_POL "nt"
-#endif
+// One 16-byte-per-lane LDS-DMA through it, issued from asm: lane offset `voff` plus the
+// wave-uniform byte offset `soff` (SGPR soffset).
 template <int NT>
 __device__ __forceinline__ void lh_dma16_bufs(const lh_u32x4r &rs, int voff, int soff, const void *lds) {
     const unsigned m = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)lds);
     if constexpr (NT)
-        asm volatile("buffer_load_dwordx4 %0, %1, %2 offen " LH_CPS_POL " lds" ::"v"(voff), "s"(rs), "s"(soff), "{m0}"(m)
+        asm volatile("buffer_load_dwordx4 %0, %1, %2 offen nt lds" ::"v"(voff), "s"(rs), "s"(soff), "{m0}"(m)
                      : "memory");
     else
         asm volatile("buffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(voff), "s"(rs), "s"(soff), "{m0}"(m) : "memory");
@@ -722,7 +674,7 @@ __device__ __forceinline__ void lh_encode_wave_lds(long long wave, const unsigne
     if (s0 >= stripes) return;  // wave-uniform
     const int nst = (int)((stripes - s0) < LH_SPW ? (stripes - s0) : LH_SPW);
     lh_ldsrc S;
-    S.ring = lh_lring[lh_wid<0>()];
+    S.ring = lh_lring[lh_wid()];
     // LH_PTR: in / out are the data and recovery pointer tables (rows of LH_K / LH_M pointers)
     __shared__ unsigned long long lh_lpt[4][LH_SPW * LH_LPR];
     unsigned long long *prow = lh_lpt[threadIdx.x >> 6];
@@ -858,9 +810,6 @@ struct lh_cps_cols {
         }
     }
 };
-#ifndef LH_CPS_AHEAD
-#define LH_CPS_AHEAD 0  // 1: two slots, step T + 1 issued before step T is combined (tools/tune.py)
-#endif
 // Step T1's DMAs into `slot` (the last step's chunks past column LH_K out of range).
 template <int T1>
 __device__ __forceinline__ void lh_cps_issue(const lh_u32x4r &rs, const int (&voff)[LH_SQ], unsigned char *slot) {
@@ -880,18 +829,6 @@ struct lh_unroll_cps {
     __device__ __forceinline__ static void run(lh_word (&acc)[LH_M][8], const lh_u32x4r &rs, const int (&voff)[LH_SQ],
                                                unsigned char *slot, int lo, int lo8) {
         if constexpr (T < LH_NSTEP) {
-#if LH_CPS_AHEAD
-            unsigned char *cur = slot + (T & 1) * LH_SSLOT;
-            if constexpr (T + 1 < LH_NSTEP) {
-                lh_cps_issue<T + 1>(rs, voff, slot + ((T + 1) & 1) * LH_SSLOT);  // (its slot was read at T - 1)
-                lh_wait_vmcnt<LH_SQ>();  // step T landed, T + 1 in flight
-            } else {
-                lh_wait_vmcnt<0>();
-            }
-            asm volatile("" ::: "memory");
-            lh_cps_cols<T, 0>::run(acc, cur, lo, lo8);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slot's reads are done
-#else
             lh_wait_vmcnt<0>();  // this step's DMAs landed (the only ones in flight)
             asm volatile("" ::: "memory");
             lh_cps_cols<T, 0>::run(acc, slot, lo, lo8);
@@ -899,60 +836,20 @@ struct lh_unroll_cps {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slot's reads are done
                 lh_cps_issue<T + 1>(rs, voff, slot);
             }
-#endif
             lh_unroll_cps<T + 1>::run(acc, rs, voff, slot, lo, lo8);
         }
     }
 };
-#ifndef LH_CPS_FLAT
-#define LH_CPS_FLAT 0  // (per-lane stores: at one workgroup per CU the slot-image stores measured slower)
-#endif
-// Recovery rows per slot image (the slot holds LH_SQ KiB).
-#define LH_CRP ((LH_SQ * 1024) / (LH_SPW * LH_BYTES) < LH_M ? (LH_SQ * 1024) / (LH_SPW * LH_BYTES) : LH_M)
-#if LH_CRP >= 1
-template <int R0>
-struct lh_cps_flat {
-    __device__ __forceinline__ static void run(const lh_word (&acc)[LH_M][8], unsigned char *slot,
-                                               unsigned char *__restrict__ out, long long out_stride, long long s0,
-                                               int nst, int sl, int c, bool last) {
-        if constexpr (R0 < LH_M) {
-            constexpr int nr = (LH_M - R0) < LH_CRP ? (LH_M - R0) : LH_CRP;
-            unsigned char *img = slot + (sl < LH_SPW ? sl : LH_SPW - 1) * (nr * LH_BYTES) + (last ? LH_SUB - 8 : 8 * c);
-#pragma unroll
-            for (int r = 0; r < nr; ++r) lh_img_row<0>(img + r * LH_BYTES, acc[R0 + r], last, sl < nst);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the image is complete
-            constexpr int per = nr * LH_BYTES / 16;  // chunks per stripe
-            const int n = nst * per, lane = threadIdx.x & 63;
-#pragma unroll
-            for (int q = 0; q < (LH_SPW * per + 63) / 64; ++q) {
-                const int j = 64 * q + lane;
-                if (j < n) {
-                    const int js = j / per, t = j - js * per;
-                    const lh_u32x4a v = *(const lh_u32x4a *)(slot + j * 16);
-                    unsigned char *dst = out + (s0 + js) * out_stride + R0 * LH_BYTES + t * 16;
-#if LH_NT_ST
-                    __builtin_nontemporal_store(v, (lh_u32x4a *)dst);
-#else
-                    *(lh_u32x4a *)dst = v;
-#endif
-                }
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slot's reads are done
-            lh_cps_flat<R0 + nr>::run(acc, slot, out, out_stride, s0, nst, sl, c, last);
-        }
-    }
-};
-#endif
 __device__ __forceinline__ void lh_encode_wave_cps(long long wave, const unsigned char *__restrict__ in,
                                                    long long in_stride, unsigned char *__restrict__ out,
                                                    long long out_stride, int stripes) {
-    __shared__ __attribute__((aligned(16))) unsigned char lh_cring[LH_WPB][(1 + LH_CPS_AHEAD) * LH_SSLOT];
+    __shared__ __attribute__((aligned(16))) unsigned char lh_cring[LH_WPB][LH_SSLOT];
     const int lane = threadIdx.x & 63;
     const int sl = lane / LH_NCH, c = lane - sl * LH_NCH;
     const long long s0 = (long long)__builtin_amdgcn_readfirstlane((int)wave) * LH_SPW;  // wave-uniform
     if (s0 >= stripes) return;  // wave-uniform
     const int nst = (int)((stripes - s0) < LH_SPW ? (stripes - s0) : LH_SPW);
-    unsigned char *slot = lh_cring[lh_wid<0>()];
+    unsigned char *slot = lh_cring[lh_wid()];
     const lh_u32x4r rs = lh_rsrc(in + s0 * in_stride, (unsigned)(nst * in_stride));
     int voff[LH_SQ];
 #pragma unroll
@@ -976,11 +873,7 @@ __device__ __forceinline__ void lh_encode_wave_cps(long long wave, const unsigne
     lh_unroll_cps<0>::run(acc, rs, voff, slot, lo, lo8);
     const bool last = c == LH_NCH - 1;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // every slot read of the last step done
-#if LH_CPS_FLAT && LH_CRP >= 1
-    // The recovery blocks leave through the slot, LH_CRP rows at a time ([stripe][row][bytes]
-    // images, 16-byte stores of contiguous runs; a stripe's rows are contiguous in memory).
-    lh_cps_flat<0>::run(acc, slot, out, out_stride, s0, nst, sl, c, last);
-#else
+    // (per-lane stores: at one workgroup per CU, stores from a slot image measured slower)
     if (sl >= nst) return;
     const int p = last ? LH_SUB - 8 : 8 * c;
     unsigned char *o = out + (s0 + sl) * out_stride + p;
@@ -1000,7 +893,6 @@ __device__ __forceinline__ void lh_encode_wave_cps(long long wave, const unsigne
             // left as partial-line writes, +14 MB per k29/m4 launch, profiles/r10x/r10y PMC)
             asm volatile("" ::: "memory");
         }
-#endif
 }
 #endif  // LH_CPS
 
@@ -1079,15 +971,7 @@ __device__ __forceinline__ void lh_encode_wave(long long wave, const unsigned ch
 #ifndef LH_FAMILY
 #define LH_FAMILY 0
 #endif
-#if LH_FAMILY
-#ifndef LH_FAM_SPLIT
-#define LH_FAM_SPLIT 0
-#endif
-#if LH_FAM_SPLIT
-#define LH_FAM_AD8 ad8[b]
-#else
-#define LH_FAM_AD8 (ad[b] + 8)
-#endif
+#if LH_FAMILY && LH_ROLE != 2
 struct lh_fam {
     int bytes, sub, nch, spw, sch, sq, r8;
 };
@@ -1099,13 +983,12 @@ struct lh_fam {
 // which with one wave per SIMD exposed the LDS latency 16 times per column (k29/m4 encode
 // 0.587 ms).
 template <int R>
-__device__ __forceinline__ void lh_fam_col(lh_word (&d)[8], const unsigned char *slot, const int (&ad)[8],
-                                           const int (&ad8)[8]) {
+__device__ __forceinline__ void lh_fam_col(lh_word (&d)[8], const unsigned char *slot, const int (&ad)[8]) {
     lh_u32x2a x[8], y[8];
 #pragma unroll
     for (int b = 0; b < 8; ++b) {
         x[b] = *(const lh_u32x2a *)(slot + ad[b] + ((b * R) & ~7));
-        if (((b * R) & 7) != 0) y[b] = *(const lh_u32x2a *)(slot + LH_FAM_AD8 + ((b * R) & ~7));
+        if (((b * R) & 7) != 0) y[b] = *(const lh_u32x2a *)(slot + (ad[b] + 8) + ((b * R) & ~7));
     }
 #pragma unroll
     for (int b = 0; b < 8; ++b) {
@@ -1127,19 +1010,17 @@ __device__ __forceinline__ void lh_fam_col(lh_word (&d)[8], const unsigned char 
         }
     }
 }
-#endif  // LH_FAMILY
-#if LH_FAMILY && LH_ROLE != 2
 #define LH_FSQ (4 * LH_CPS)  // DMA instructions per step, at most
 template <int T, int CC, int R>
 struct lh_fam_cols {
     __device__ __forceinline__ static void run(lh_word (&acc)[LH_M][8], const unsigned char *slot,
-                                               const int (&ad)[LH_CPS][8], const int (&ad8)[LH_CPS][8]) {
+                                               const int (&ad)[LH_CPS][8]) {
         if constexpr (CC < LH_CPS && T * LH_CPS + CC < LH_K) {
             lh_word d[8];
-            lh_fam_col<R>(d, slot, ad[CC], ad8[CC]);
+            lh_fam_col<R>(d, slot, ad[CC]);
             lh_column<T * LH_CPS + CC>(acc, d);
             lh_opaque(acc);
-            lh_fam_cols<T, CC + 1, R>::run(acc, slot, ad, ad8);
+            lh_fam_cols<T, CC + 1, R>::run(acc, slot, ad);
         }
     }
 };
@@ -1147,11 +1028,11 @@ template <int T, int R>
 struct lh_unroll_fam {
     __device__ __forceinline__ static void run(lh_word (&acc)[LH_M][8], const lh_u32x4r &rs, const int (&voff)[LH_FSQ],
                                                const int (&voffl)[LH_FSQ], unsigned char *slot, const lh_fam &F,
-                                               const int (&ad)[LH_CPS][8], const int (&ad8)[LH_CPS][8]) {
+                                               const int (&ad)[LH_CPS][8]) {
         if constexpr (T < LH_NSTEP) {
             lh_wait_vmcnt<0>();  // this step's DMAs landed (the only ones in flight)
             asm volatile("" ::: "memory");
-            lh_fam_cols<T, 0, R>::run(acc, slot, ad, ad8);
+            lh_fam_cols<T, 0, R>::run(acc, slot, ad);
             if constexpr (T + 1 < LH_NSTEP) {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slot's reads are done
                 const int x1b = (T + 1) * LH_CPS * F.bytes;
@@ -1166,7 +1047,7 @@ struct lh_unroll_fam {
                     }
                 }
             }
-            lh_unroll_fam<T + 1, R>::run(acc, rs, voff, voffl, slot, F, ad, ad8);
+            lh_unroll_fam<T + 1, R>::run(acc, rs, voff, voffl, slot, F, ad);
         }
     }
 };
@@ -1228,21 +1109,15 @@ __device__ __forceinline__ void lh_encode_wave_fam(long long wave, const lh_fam 
             for (int i = 0; i < LH_NW; ++i) acc[r][y].v[i] = 0;
     const int lo = (sl < F.spw ? sl : F.spw - 1) * (LH_CPS * F.bytes) + 8 * c;
     // column cc, sub-block b: lo + cc bytes + b (sub - R) (the constant part in the reads).
-    // LH_FAM_SPLIT: the second word's address in registers of its own, hidden from the compiler
-    // (two ds_read_b64, 2 LDS cycles each, instead of one ds_read2_b64, 8) -- measured slower
-    // here (0.540 against 0.529 ms), unlike in the size-specialised kernels.
-    int ad[LH_CPS][8], ad8[LH_CPS][8];
+    // (The second word's address in registers of its own, hidden from the compiler -- two
+    // ds_read_b64, 2 LDS cycles each, instead of one ds_read2_b64, 8 -- measured slower here,
+    // 0.540 against 0.529 ms, unlike in the size-specialised kernels.)
+    int ad[LH_CPS][8];
 #pragma unroll
     for (int cc = 0; cc < LH_CPS; ++cc)
 #pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            ad[cc][b] = lo + cc * F.bytes + b * (F.sub - R);
-            ad8[cc][b] = ad[cc][b] + 8;
-#if LH_FAM_SPLIT
-            asm volatile("" : "+v"(ad8[cc][b]));
-#endif
-        }
-    lh_unroll_fam<0, R>::run(acc, rs, voff, voffl, slot, F, ad, ad8);
+        for (int b = 0; b < 8; ++b) ad[cc][b] = lo + cc * F.bytes + b * (F.sub - R);
+    lh_unroll_fam<0, R>::run(acc, rs, voff, voffl, slot, F, ad);
     if (sl >= nst) return;
     const bool last = c == F.nch - 1;
     unsigned char *o = out + (s0 + sl) * out_stride + (last ? F.sub - 8 : 8 * c);
@@ -1338,9 +1213,6 @@ __device__ __forceinline__ void lh_load_packed(unsigned int (&w)[N], const unsig
 #define LH_DCOLS (LH_K + LH_M)
 #ifndef LH_PF_DEC
 #define LH_PF_DEC 1  // decode prefetch depth (tools/tune.py, fused plan: 1 >= 2 > 3)
-#endif
-#ifndef LH_PREP_FIRST
-#define LH_PREP_FIRST 0  // fused decode: solve the plan before (1) or while (0) the first columns load
 #endif
 #if LH_BUF
 // Column source of a wave: one buffer resource over the wave's stripes (wave-uniform base,
@@ -1604,14 +1476,9 @@ __device__ __forceinline__ void lh_decode_body(const lh_lane &l, long long wave,
     const lh_dsrc S = lh_make_dsrc(l, wave, blocks, stripe_stride, zero_page, stripes);
     lh_word v[LH_M][8];
     {
-#if LH_PREP_FIRST
-        prep(pr);  // solve before the first loads: the ring is not live across the solve
-#endif
         lh_word ring[PF][8];
         lh_dec_issue<PF>(ring, pr, S);
-#if !LH_PREP_FIRST
         prep(pr);
-#endif
         lh_dec_phase_a<PF>(v, ring, pr, S);
     }
 #if LH_BUF
@@ -1658,9 +1525,8 @@ lh_jit_decode(unsigned char *__restrict__ blocks, long long stripe_stride,
 // assignment (:786); duplicate / out-of-range rows mark the stripe invalid, untouched.
 #if LH_EMAX <= 4 && LH_NCH <= 64 && LH_K <= 64
 #define LH_FUSED 1
-#ifndef LH_DWPB
-#define LH_DWPB 4  // waves per workgroup of the fused decode (strided batches; jit.cpp dec_wpb)
-#endif
+#undef LH_DWPB
+#define LH_DWPB 4  // waves per workgroup of the fused decode (the host launches 256 threads; no knob)
 static constexpr unsigned char LH_GRAW[LH_M][LH_K] = LH_G_INIT;
 #define LH_P4(n) (((n) + 3) / 4 * 4)
 #define LH_SR (2 * LH_P4(LH_K) + LH_P4(LH_M))  // per-stripe scratch: rows | src map | rec map
@@ -1689,12 +1555,6 @@ __device__ __forceinline__ void lh_fused_rows(const G &g, const lh_lane &l, int 
     }
 }
 
-__device__ __forceinline__ unsigned int lh_gmul(const unsigned char *gexp, const short *glog, unsigned int a,
-                                                unsigned int b) {
-    return (a && b) ? gexp[glog[a] + glog[b]] : 0u;
-}
-
-// Returns false when the stripe has nothing to do (no erasure or invalid rows).
 // Part 2 of the fused plan (run while the first columns load): invert, pack, rewrite rows.
 struct lh_fused_solve {
     unsigned int rs[LH_EMAX], rr[LH_EMAX], er[LH_EMAX];
@@ -1766,10 +1626,7 @@ __device__ __forceinline__ bool lh_fused_plan(const G &g, const lh_lane &l, int 
         if (c == 0 && status) status[l.stripe] = -1;
         return false;
     }
-#ifndef LH_PROBE_NOMETA
-#define LH_PROBE_NOMETA 0  // (probe, wrong rows / status: neither written -- their share of the HBM writes)
-#endif
-    if (c == 0 && status && !LH_PROBE_NOMETA) status[l.stripe] = 0;
+    if (c == 0 && status) status[l.stripe] = 0;
     pr.e = nr;
     if (nr == 0) return false;
 #pragma unroll
@@ -1782,10 +1639,6 @@ __device__ __forceinline__ bool lh_fused_plan(const G &g, const lh_lane &l, int 
     for (int q = 0; q < LH_NREC; ++q) pr.recw[q] = ((const unsigned int *)lrec)[q];
     return true;
 }
-
-#ifndef LH_SOLVE_GJ
-#define LH_SOLVE_GJ 0  // fused planner: Gauss-Jordan instead of the adjugate inverse (A/B knob)
-#endif
 
 // Permutations of n <= 3 elements, for the cofactor expansion below.
 template <int n> struct lh_perms;
@@ -1870,38 +1723,7 @@ __device__ __forceinline__ void lh_fused_solve::operator()(lh_plan_regs &pr) con
 #pragma unroll
         for (int j = 0; j < LH_EMAX; ++j)
             A[i][j] = (i < nr && j < nr) ? gmat[rr[i] * LH_K + er[j]] : (i == j ? 1u : 0u);
-#if LH_SOLVE_GJ  // Gauss-Jordan (round 1): one dependent chain of table lookups per step
-#pragma unroll
-    for (int i = 0; i < LH_EMAX; ++i)
-#pragma unroll
-        for (int j = 0; j < LH_EMAX; ++j) I[i][j] = (i == j) ? 1u : 0u;
-#pragma unroll
-    for (int cc = 0; cc < LH_EMAX; ++cc) {
-        int p = cc;
-#pragma unroll
-        for (int r = LH_EMAX - 1; r >= cc; --r) if (A[r][cc]) p = r;
-#pragma unroll
-        for (int r = cc + 1; r < LH_EMAX; ++r)
-            if (r == p)
-#pragma unroll
-                for (int j = 0; j < LH_EMAX; ++j) {
-                    unsigned int t = A[cc][j]; A[cc][j] = A[r][j]; A[r][j] = t;
-                    t = I[cc][j]; I[cc][j] = I[r][j]; I[r][j] = t;
-                }
-        const unsigned int inv = gexp[255 - glog[A[cc][cc]]];
-#pragma unroll
-        for (int j = 0; j < LH_EMAX; ++j) { A[cc][j] = lh_gmul(gexp, glog, A[cc][j], inv); I[cc][j] = lh_gmul(gexp, glog, I[cc][j], inv); }
-#pragma unroll
-        for (int r = 0; r < LH_EMAX; ++r) {
-            if (r == cc) continue;
-            const unsigned int f = A[r][cc];
-#pragma unroll
-            for (int j = 0; j < LH_EMAX; ++j) { A[r][j] ^= lh_gmul(gexp, glog, f, A[cc][j]); I[r][j] ^= lh_gmul(gexp, glog, f, I[cc][j]); }
-        }
-    }
-#else
     lh_inv_adj<LH_EMAX>(A, I, gexp, glog);
-#endif
 #pragma unroll
     for (int i = 0; i < LH_EMAX; ++i)
 #pragma unroll
@@ -1926,7 +1748,7 @@ __device__ __forceinline__ void lh_fused_solve::operator()(lh_plan_regs &pr) con
     // Recovery slot i takes missing row er[i] (reference generate_bitmatrix, :786).
     if (c == 0)
 #pragma unroll
-        for (int i = 0; i < LH_EMAX; ++i) if (i < nr && !LH_PROBE_NOMETA) grow[rs[i]] = (unsigned char)er[i];
+        for (int i = 0; i < LH_EMAX; ++i) if (i < nr) grow[rs[i]] = (unsigned char)er[i];
     // Materialise the packed plan here, so the solve's matrices die before phase A: left
     // alone, the compiler sinks the packing into phase B and keeps the e x e inverse and
     // the row lists live across all k + m columns (k29/m4: 218 -> 158 VGPRs, 2 -> 3
@@ -1967,17 +1789,11 @@ struct lh_dmoff {  // scratch offset of column X's slot byte
     using D = lh_dcol<X, LH_LDS_REC_FIRST>;
     static constexpr int v = D::rec ? LH_SR_REC + D::r : LH_SR_SRC + D::x;
 };
-#ifndef LH_DOPQ
-#define LH_DOPQ 0  // the DMAs' LDS offsets opaque where used (no SGPR held per slot / chunk address)
-#endif
 struct lh_dldsrc {
 #if LH_PTR
     const unsigned long long *pt;  // LDS: the wave's pointer rows [stripe][LH_K + 1]
     int prow[LH_LQ];               // DMA chunk q: its stripe's row in pt
     int joff[LH_LQ];               // ... its offset in the block
-#elif LH_ASM_DMA
-    lh_u32x4r rs;
-    int joff[LH_LQ];  // DMA chunk q: byte offset in the wave's stripes (block 0)
 #else
     __amdgpu_buffer_rsrc_t rs;
     int joff[LH_LQ];  // DMA chunk q: byte offset in the wave's stripes (block 0)
@@ -1999,17 +1815,10 @@ struct lh_dldsrc {
 #if LH_PTR
             lh_dma16<LH_LDS_NT_DEC>((const unsigned char *)pt[prow[q] + (sv[q] == 0xFFu ? LH_K : (int)sv[q])] + joff[q],
                                     ring + slot * (LH_LQ * 1024) + q * 1024);
-#elif LH_ASM_DMA
-            lh_dma16_buf<LH_LDS_NT_DEC>(rs, sv[q] == 0xFFu ? (int)0x80000000 : joff[q] + (int)sv[q] * LH_BYTES,
-                                        ring + slot * (LH_LQ * 1024) + q * 1024);
 #else
-        {
-            int off = slot * (LH_LQ * 1024) + q * 1024;
-            if (LH_DOPQ) asm volatile("" : "+s"(off));  // (opaque: see lh_fdsrc::issue)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(
-                rs, (__attribute__((address_space(3))) void *)(ring + off), 16,
+                rs, (__attribute__((address_space(3))) void *)(ring + slot * (LH_LQ * 1024) + q * 1024), 16,
                 sv[q] == 0xFFu ? (int)0x80000000 : joff[q] + (int)sv[q] * LH_BYTES, 0, 0, LH_LDS_NT_DEC ? 2 : 0);
-        }
 #endif
     }
 };
@@ -2080,24 +1889,12 @@ __device__ __forceinline__ void lh_decode_lds_prologue(const lh_dldsrc &S) {
 // Phase B and the stores of a stripe's recovered blocks: block i = sum_r coef[i][r] V_r, stored
 // at the slot `dst(out slot i)` returns (the lane's chunk of it); the last lane of a stripe
 // funnels the previous lane's word (its chunk's last LH_VLAST bytes are its own).
-#ifndef LH_PROBE_NOPB
-#define LH_PROBE_NOPB 0
-#endif
-#ifndef LH_DEC_ST_PEND
-#define LH_DEC_ST_PEND 0  // (1: measured no change in write bytes, decode 0.5548 -> 0.5598 ms; profiles/r10w_*)
-#endif
 // (VL: the last lane's own bytes, sub: the sub-block size -- LH_VLAST, LH_SUB except in the
 // block-size family)
 template <int VL, class DST>
 __device__ __forceinline__ void lh_fused_out_g(const lh_word (&v)[LH_M][8], const lh_plan_regs &pr, bool last, int sub,
                                                DST dst) {
     const int e = pr.e;
-#if LH_DEC_ST_PEND
-    lh_word pend;  // the last block's last sub-row, stored with the next block
-    unsigned char *pd = nullptr;
-#pragma unroll
-    for (int q = 0; q < LH_NW; ++q) pend.v[q] = 0;
-#endif
 #pragma unroll
     for (int i = 0; i < LH_EMAX; ++i) {
         if (i < e) {  // stripe-uniform: the funnel's source lane is active too
@@ -2106,10 +1903,6 @@ __device__ __forceinline__ void lh_fused_out_g(const lh_word (&v)[LH_M][8], cons
             for (int y = 0; y < 8; ++y)
 #pragma unroll
                 for (int q = 0; q < LH_NW; ++q) o[y].v[q] = 0;
-#if LH_PROBE_NOPB  // (probe, wrong bytes: no phase B, V_(i mod m) stored as block i -- what phase B costs)
-#pragma unroll
-            for (int y = 0; y < 8; ++y) o[y] = v[i % LH_M][y];
-#else
 #pragma unroll
             for (int t = 7; t >= 0; --t) {
                 if (t != 7) {
@@ -2136,18 +1929,9 @@ __device__ __forceinline__ void lh_fused_out_g(const lh_word (&v)[LH_M][8], cons
                 lh_pin8(o);
 #endif
             }
-#endif
             unsigned char *d = dst((int)LH_BYTE(pr.outw, i));
-#if LH_DEC_ST_PEND
-            // the previous block's last sub-row right before this block's first: when the two
-            // blocks are neighbours (the recovery slots usually are), the line they share gets
-            // both parts back to back instead of a block's phase B apart (non-temporal stores
-            // leave the earlier part as a partial-line write)
-            if (i > 0) {
-                lh_store(pd + 7 * sub, pend);
-                asm volatile("" ::: "memory");
-            }
-#endif
+            // (Holding a block's last sub-row back to store it right before the next block's
+            // first measured slower, write bytes unchanged: profiles/r10w_store_order_k29m4.txt.)
 #pragma unroll
             for (int y = 0; y < 8; ++y) {
                 lh_word w = o[y];
@@ -2156,21 +1940,11 @@ __device__ __forceinline__ void lh_fused_out_g(const lh_word (&v)[LH_M][8], cons
                     w.v[0] = last ? f.v[0] : w.v[0];
                     w.v[1] = last ? f.v[1] : w.v[1];
                 }
-#if LH_DEC_ST_PEND
-                if (y == 7) {
-                    pend = w;
-                    pd = d;
-                    continue;
-                }
-#endif
                 lh_store(d + y * sub, w);
                 asm volatile("" ::: "memory");
             }
         }
     }
-#if LH_DEC_ST_PEND
-    if (e > 0) lh_store(pd + 7 * sub, pend);
-#endif
 }
 template <class DST>
 __device__ __forceinline__ void lh_fused_out(const lh_word (&v)[LH_M][8], const lh_plan_regs &pr, bool last, DST dst) {
@@ -2207,14 +1981,10 @@ __device__ __forceinline__ void lh_fused_wave_lds(const lh_lane &l, long long wa
     S.pt = prow;
 #else
     (void)zero_page;
-#if LH_ASM_DMA
-    S.rs = lh_rsrc(blocks + s0 * stripe_stride, (unsigned)(nst * stripe_stride));
-#else
     S.rs = __builtin_amdgcn_make_buffer_rsrc(blocks + s0 * stripe_stride, 0, (int)(nst * stripe_stride), 0x00020000);
 #endif
-#endif
     S.scr = scr;
-    S.ring = lh_dring[lh_wid<1>()];
+    S.ring = lh_dring[(int)(threadIdx.x >> 6)];  // (per-lane to the compiler on purpose: see lh_wid)
 #pragma unroll
     for (int q = 0; q < LH_LQ; ++q) {
         int j = 64 * q + lane;
@@ -2257,205 +2027,6 @@ __device__ __forceinline__ void lh_fused_wave_lds(const lh_lane &l, long long wa
 }
 #endif  // LH_LDS
 
-// ------------------------------------------------------------ memory-order decode (LH_DMO)
-// The fused decode above reads a stripe's slots in row order (its networks are compiled per
-// row), so in a shuffled stripe each slot is a lone 1 296-byte run and the 64-byte sector two
-// neighbouring slots share is fetched once per slot: k29/m4 HBM traffic 1.075x the algorithmic
-// bytes (profiles/r9g_pmc_k29m4_decode_variants.txt).  LH_DMO = 1 reads the slots in memory
-// order instead, LH_CPS slots of every stripe per step (one contiguous run per stripe, as the
-// multi-column encode), and runs each slot's network by its row, known only at run time: the
-// wave takes the rows present at that slot one at a time (a stripe's lanes hold one row; the
-// wave's stripes usually hold different ones), each through a binary tree of wave-uniform
-// branches down to the row's compile-time network, executed by the lanes holding that row.
-// The networks cost up to LH_SPW times their VALU work of the row-order form -- affordable, the
-// decode's VALU runs below 10 % of its time -- for the encode's memory stream.  Strided batches
-// (LH_PTR keeps the row-order form); plan, solve, phase B and stores as above.
-#ifndef LH_DMO
-#define LH_DMO 0
-#endif
-#if LH_DMO && !(LH_LDS && LH_CPS > 1 && !LH_PTR && defined(LH_FUSED))
-#undef LH_DMO
-#define LH_DMO 0
-#endif
-#if LH_DMO
-#ifndef LH_DMO_AHEAD
-#define LH_DMO_AHEAD 1  // two step slots: step T + 1 lands while step T is combined
-#endif
-// Row r's contribution (wave-uniform r < LH_DCOLS): original column r's network, or recovery
-// row r - LH_K XORed into V_(r - LH_K).  The dispatch is a sequence of one-sided uniform tests,
-// first on r / 8, then on r, each test against r passed through an empty asm so the compiler
-// cannot chain them into a switch: a branch tree (an if / else nest or a lowered switch) is
-// structurised with flow blocks whose paths carry the accumulators past the leaves, and each
-// such path cost up to 64 register copies; a one-sided test updates them in place.
-#ifndef LH_DMO_PROBE
-#define LH_DMO_PROBE 0  // (probes, wrong bytes: 1 no dispatch, one XOR per slot; 2 the dispatch with one-XOR leaves)
-#endif
-template <int X>
-__device__ __forceinline__ void lh_rowleaf(lh_word (&v)[LH_M][8], const lh_word (&d)[8]) {
-    if constexpr (LH_DMO_PROBE == 2) {
-#pragma unroll
-        for (int y = 0; y < 8; ++y) lh_xor(v[X % LH_M][y], d[(y + X) & 7]);
-    } else if constexpr (X < LH_K) {
-        lh_column<X>(v, d);
-    } else {
-#pragma unroll
-        for (int y = 0; y < 8; ++y) lh_xor(v[X - LH_K][y], d[y]);
-    }
-    asm volatile("; row %0" ::"i"(X));  // (a leaf of its own: no merging of leaves by the compiler)
-}
-template <int X, int END>
-struct lh_rowgrp {
-    __device__ __forceinline__ static void run(unsigned r, lh_word (&v)[LH_M][8], const lh_word (&d)[8]) {
-        if constexpr (X < END) {
-            asm volatile("" : "+s"(r));
-            if (r == (unsigned)X) lh_rowleaf<X>(v, d);
-            lh_rowgrp<X + 1, END>::run(r, v, d);
-        }
-    }
-};
-template <int G>
-struct lh_rowdisp {
-    __device__ __forceinline__ static void run(unsigned r, lh_word (&v)[LH_M][8], const lh_word (&d)[8]) {
-        if constexpr (8 * G < LH_DCOLS) {
-            unsigned g = r >> 3;
-            asm volatile("" : "+s"(g));
-            if (g == (unsigned)G) lh_rowgrp<8 * G, (8 * G + 8 < LH_DCOLS ? 8 * G + 8 : LH_DCOLS)>::run(r, v, d);
-            lh_rowdisp<G + 1>::run(r, v, d);
-        }
-    }
-};
-// The lane's 8 words of one slot in the ring (`col` its run-time address): every read issued
-// before any is used (a wait per read, placed by the compiler next to each use, exposes the
-// LDS latency 8 times per slot with one wave per SIMD; as lh_fam_col).
-template <int B>
-__device__ __forceinline__ void lh_dmo_rd(lh_u32x2a (&x)[8], lh_u32x2a (&y)[8], const unsigned char *col, int lo, int lo8) {
-    if constexpr (B < 8) {
-        constexpr int S = (B * LH_SUB) % 8, O = B * LH_SUB - S;
-        x[B] = *(const lh_u32x2a *)(col + lo + O);
-        if constexpr (S != 0) y[B] = *(const lh_u32x2a *)(col + lo8 + O);
-        lh_dmo_rd<B + 1>(x, y, col, lo, lo8);
-    }
-}
-template <int B>
-__device__ __forceinline__ void lh_dmo_fn(lh_word (&d)[8], const lh_u32x2a (&x)[8], const lh_u32x2a (&y)[8]) {
-    if constexpr (B < 8) {
-        constexpr int S = (B * LH_SUB) % 8;
-        if constexpr (S == 0) {
-            d[B].v[0] = x[B].x;
-            d[B].v[1] = x[B].y;
-        } else {
-            d[B] = lh_funnel<S>(x[B].x, x[B].y, y[B].x, y[B].y);
-        }
-        lh_dmo_fn<B + 1>(d, x, y);
-    }
-}
-__device__ __forceinline__ void lh_dmo_col(lh_word (&d)[8], const unsigned char *col, int lo, int lo8) {
-    lh_u32x2a x[8], y[8];
-    lh_dmo_rd<0>(x, y, col, lo, lo8);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-        asm volatile("" : "+v"(x[b]));
-        if ((b * LH_SUB) % 8 != 0) asm volatile("" : "+v"(y[b]));
-    }
-    lh_dmo_fn<0>(d, x, y);
-}
-// Step t's DMAs (slots t LH_CPS .. of every working stripe) into `ring`; in the last step the
-// chunks past slot LH_K are out of range.
-__device__ __forceinline__ void lh_dmo_issue(const lh_u32x4r &rs, const int (&voff)[LH_SQ], int t, unsigned char *ring) {
-    const int lane = threadIdx.x & 63;
-    const bool lastep = t + 1 == LH_NSTEP;
-#pragma unroll
-    for (int q = 0; q < LH_SQ; ++q) {
-        int v = voff[q];
-        if (LH_LASTC < LH_CPS && lastep) v = ((64 * q + lane) % LH_SCH) < LH_LASTC * LH_CCH ? v : (int)0x80000000;
-        lh_dma16_bufs<LH_LDS_NT_DEC>(rs, v, t * (LH_CPS * LH_BYTES), ring + q * 1024);
-    }
-}
-__device__ __forceinline__ void lh_fused_wave_dmo(const lh_lane &l, long long wave, int c, int sl, bool work,
-                                                  const unsigned char *scr, unsigned char *__restrict__ blocks,
-                                                  long long stripe_stride, int stripes, const lh_fused_solve &sv,
-                                                  lh_plan_regs &pr) {
-    __shared__ __attribute__((aligned(16))) unsigned char lh_mring[LH_DWPB][(1 + LH_DMO_AHEAD) * LH_SSLOT];
-    const int lane = threadIdx.x & 63;
-    const long long s0 = (long long)__builtin_amdgcn_readfirstlane((int)wave) * LH_SPW;  // wave-uniform
-    if (s0 >= stripes) return;  // wave-uniform
-    const int nst = (int)((stripes - s0) < LH_SPW ? (stripes - s0) : LH_SPW);
-    const unsigned long long wm = __ballot(work);
-    if (wm == 0) return;  // wave-uniform
-    unsigned char *ring = lh_mring[lh_wid<1>()];
-    const lh_u32x4r rs = lh_rsrc(blocks + s0 * stripe_stride, (unsigned)(nst * stripe_stride));
-    int voff[LH_SQ];  // chunk j = 64 q + lane of the step image [stripe][LH_CPS x bytes]
-#pragma unroll
-    for (int q = 0; q < LH_SQ; ++q) {
-        const int j = 64 * q + lane, js = j / LH_SCH, r = j - js * LH_SCH;
-        const bool on = js < nst && ((wm >> (js * LH_NCH)) & 1ull);  // (a stripe with nothing to do: no reads)
-        voff[q] = on ? js * (int)stripe_stride + r * 16 : (int)0x80000000;
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the previous group's ring reads are done
-    lh_dmo_issue(rs, voff, 0, ring);
-    if (work) sv(pr);  // the solve, while the first step lands
-    lh_word v[LH_M][8];
-#pragma unroll
-    for (int r = 0; r < LH_M; ++r)
-#pragma unroll
-        for (int y = 0; y < 8; ++y)
-#pragma unroll
-            for (int i = 0; i < LH_NW; ++i) v[r][y].v[i] = 0;
-    const int sc = sl < LH_SPW ? sl : LH_SPW - 1;
-    const int lo = sc * (LH_CPS * LH_BYTES) + 8 * c;
-    int lo8 = lo + 8;
-    asm volatile("" : "+v"(lo8));
-    const unsigned char *lrows = scr + sc * LH_SR;  // the lane's stripe's slot rows (lh_fused_plan)
-#pragma unroll 1
-    for (int t = 0; t < LH_NSTEP; ++t) {
-#if LH_DMO_AHEAD
-        unsigned char *cur = ring + (t & 1) * LH_SSLOT;
-        if (t + 1 < LH_NSTEP) {
-            lh_dmo_issue(rs, voff, t + 1, ring + ((t + 1) & 1) * LH_SSLOT);  // (its slot's reads ended at t - 1)
-            lh_wait_vmcnt<LH_SQ>();  // step t landed, t + 1 in flight
-        } else {
-            lh_wait_vmcnt<0>();
-        }
-#else
-        unsigned char *cur = ring;
-        lh_wait_vmcnt<0>();  // this step's DMAs landed (the only ones in flight)
-#endif
-        asm volatile("" ::: "memory");  // no LDS read moves above the wait
-        const int ncol = t + 1 < LH_NSTEP ? LH_CPS : LH_LASTC;
-#pragma unroll 1
-        for (int cc = 0; cc < ncol; ++cc) {
-            lh_word d[8];
-            lh_dmo_col(d, cur + cc * LH_BYTES, lo, lo8);
-            const unsigned row = work ? (unsigned)lrows[t * LH_CPS + cc] : 0xFFu;
-            unsigned long long rem = wm;
-            if (LH_DMO_PROBE == 1) {
-#pragma unroll
-                for (int y = 0; y < 8; ++y) lh_xor(v[0][y], d[y]);
-                rem = 0;
-            }
-            while (rem) {  // wave-uniform: one pass per distinct row among the working lanes
-                const unsigned r = (unsigned)__builtin_amdgcn_readlane((int)row, (int)__builtin_ctzll(rem));
-                // (the test through an opaque difference: from `row == r` the compiler would
-                // substitute the lane's row for r under the branch, making the tree per-lane)
-                unsigned diff = row ^ r;
-                asm volatile("" : "+v"(diff));
-                const bool mine = diff == 0u;
-                rem &= ~__ballot(mine);
-                if (mine) lh_rowdisp<0>::run(r, v, d);
-            }
-            lh_dopaque(v);
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slot's reads are done
-#if !LH_DMO_AHEAD
-        if (t + 1 < LH_NSTEP) lh_dmo_issue(rs, voff, t + 1, ring);
-#endif
-    }
-    if (!work) return;
-    unsigned char *base = blocks + l.stripe * stripe_stride + (l.last ? LH_SUB - 8 : 8 * c);
-    lh_fused_out(v, pr, l.last, [&](int slot) { return base + (long long)slot * LH_BYTES; });
-}
-#endif  // LH_DMO
-
 #ifndef LH_DEC_LB
 #define LH_DEC_LB 1  // min waves per SIMD the register allocator must allow (tools/tune.py)
 #endif
@@ -2489,10 +2060,7 @@ __device__ __forceinline__ void lh_fused_body(unsigned char *__restrict__ blocks
         sv.gmat = gmat;
         unsigned int rowv[lh_gct::maxrw];
         lh_fused_rows(lh_gct(), l, c, rows, rowv);
-#if LH_DMO
-        const bool work = l.active && lh_fused_plan(lh_gct(), l, c, sl, &scratch[wid][sl][0], rowv, rows, status, sv, pr);
-        lh_fused_wave_dmo(l, lh_w, c, sl, work, &scratch[wid][0][0], blocks, stripe_stride, stripes, sv, pr);
-#elif LH_LDS
+#if LH_LDS
         const bool work = l.active && lh_fused_plan(lh_gct(), l, c, sl, &scratch[wid][sl][0], rowv, rows, status, sv, pr);
         lh_fused_wave_lds(l, lh_w, c, sl, work, &scratch[wid][0][0], blocks, stripe_stride, stripes, sv, pr, zero_page);
 #else
@@ -2573,10 +2141,8 @@ __device__ __forceinline__ void lh_fdissue(const lh_fdsrc &S, const unsigned (&s
         lh_fdissue<C + 1, N - 1>(S, sv);
     }
 }
-#ifndef LH_DFAM_PIN
-#define LH_DFAM_PIN 0  // 1: a column's 16 LDS reads all issued before any is used (lh_fam_col)
-#endif
-// A column's words, each read next to its use (the compiler's schedule).
+// A column's words, each read next to its use (the compiler's schedule; the encode's family
+// issues all 16 reads first, lh_fam_col).
 template <int R>
 __device__ __forceinline__ void lh_dfam_col(lh_word (&d)[8], const unsigned char *slot, const int (&ad)[8]) {
 #pragma unroll
@@ -2597,7 +2163,7 @@ __device__ __forceinline__ void lh_dfam_col(lh_word (&d)[8], const unsigned char
 // Phase A over the k + m columns, as lh_unroll_decode_lds (refills of LH_LDG slots).
 template <int X, int R>
 struct lh_unroll_dfam {
-    __device__ __forceinline__ static void run(lh_word (&v)[LH_M][8], const lh_fdsrc &S, const int (&ad)[8], const int (&ad8)[8]) {
+    __device__ __forceinline__ static void run(lh_word (&v)[LH_M][8], const lh_fdsrc &S, const int (&ad)[8]) {
         if constexpr (X < LH_DCOLS) {
             constexpr int issued = (LH_LD + LH_LDG * (X / LH_LDG)) < LH_DCOLS ? (LH_LD + LH_LDG * (X / LH_LDG)) : LH_DCOLS;
             constexpr int ahead = issued - 1 - X;
@@ -2609,11 +2175,7 @@ struct lh_unroll_dfam {
             lh_wait_vmcnt<4 * ahead>();
             asm volatile("" ::: "memory");  // no LDS read moves above the wait
             lh_word d[8];
-#if LH_DFAM_PIN
-            lh_fam_col<R>(d, S.ring + (X % LH_LD) * LH_FRS, ad, ad8);
-#else
             lh_dfam_col<R>(d, S.ring + (X % LH_LD) * LH_FRS, ad);
-#endif
             lh_dcombine<X, LH_LDS_REC_FIRST>(v, d);
             lh_dopaque(v);
             if constexpr (LH_LDG == 1 && X + LH_LD < LH_DCOLS) {
@@ -2623,7 +2185,7 @@ struct lh_unroll_dfam {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slots' reads are done
                 lh_fdissue<LH_LD + X + 1 - LH_LDG, LH_LDG>(S, svg);
             }
-            lh_unroll_dfam<X + 1, R>::run(v, S, ad, ad8);
+            lh_unroll_dfam<X + 1, R>::run(v, S, ad);
         }
     }
 };
@@ -2671,16 +2233,10 @@ __device__ __forceinline__ void lh_fused_wave_fam(const lh_dfam &F, const lh_lan
 #pragma unroll
             for (int i = 0; i < LH_NW; ++i) v[r][y].v[i] = 0;
     const int lo = (sl < F.spw ? sl : F.spw - 1) * F.bytes + 8 * c;
-    int ad[8], ad8[8];
+    int ad[8];
 #pragma unroll
-    for (int b = 0; b < 8; ++b) {
-        ad[b] = lo + b * (F.sub - R);
-        ad8[b] = ad[b] + 8;
-#if LH_FAM_SPLIT
-        asm volatile("" : "+v"(ad8[b]));
-#endif
-    }
-    lh_unroll_dfam<0, R>::run(v, S, ad, ad8);
+    for (int b = 0; b < 8; ++b) ad[b] = lo + b * (F.sub - R);
+    lh_unroll_dfam<0, R>::run(v, S, ad);
     if (!work) return;
     unsigned char *base = blocks + l.stripe * stripe_stride + (l.last ? F.sub - 8 : 8 * c);
     lh_fused_out_g<R == 0 ? 8 : R>(v, pr, l.last, F.sub, [&](int slot) { return base + (long long)slot * F.bytes; });

@@ -43,6 +43,26 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(check, name) and not hasattr(lib, name), name
 
 
+def test_jit_knobs_match_integration_doc():
+    """The `#ifndef LH_*` tunables of jit_codec.hip are exactly the knobs INTEGRATION.md section 6
+    lists for it: a knob added to, or deleted from, one of the two shows up here."""
+    csrc = os.path.join(REPO, "longhair_amd", "csrc")
+    source = open(os.path.join(csrc, "jit_codec.hip")).read()
+    in_file = set(re.findall(r"^\s*#\s*ifndef\s+(LH_\w+)", source, flags=re.M))
+    # not tunables: the guards of what jit.cpp defines for every module (the shape, the role)
+    shape = {"LH_K", "LH_ROLE"}
+    host = open(os.path.join(csrc, "jit.cpp")).read()
+    assert all("#define %s " % name in host for name in shape)
+    assert shape <= in_file
+    doc = open(os.path.join(REPO, "INTEGRATION.md")).read()
+    section = doc[doc.index("## 6. Environment knobs"):]
+    para = section[section.index("knobs of `jit_codec.hip`:"):]
+    para = para[:para.index("\n\n")]
+    in_doc = set(re.findall(r"`(LH_\w+)(?:=\w+)?`", para))
+    assert in_doc, "INTEGRATION.md section 6: the jit_codec.hip knob paragraph was not found"
+    assert in_file - shape == in_doc, (sorted(in_file - shape - in_doc), sorted(in_doc - in_file))
+
+
 def test_block_layout_matches_reference():
     import longhair_amd
     assert ctypes.sizeof(longhair_amd.Block) == 16

@@ -673,19 +673,10 @@ KNOB_VARIANTS = [
     # the decode ring refilled one and three slots at a time (default two, LH_LDG)
     ("defines-ldg1", {"LONGHAIR_AMD_JIT_DEFINES": "LH_LDG=1"}, ["lh_jit_decode_fused"]),
     ("defines-ldg3", {"LONGHAIR_AMD_JIT_DEFINES": "LH_LDG=3"}, ["lh_jit_decode_fused"]),
-    # DMAs from asm (no compiler drain: the rings really run LH_LD - 1 columns deep, counted waits)
-    ("defines-asm-dma", {"LONGHAIR_AMD_JIT_DEFINES": "LH_ASM_DMA=1"}, ["lh_jit_decode_fused"]),
-    # the encode's one-column ring (LH_CPS=1; the pointer-table encode's form) and other
-    # multi-column-step shapes: 3 columns (partial last step), 2-wave workgroups, two slots,
-    # slot-image stores
+    # the encode's one-column ring (LH_CPS=1; the pointer-table encode's form) and another
+    # multi-column-step shape: 3 columns (partial last step), 2-wave workgroups
     ("defines-cps1", {"LONGHAIR_AMD_JIT_DEFINES": "LH_CPS=1"}, ["lh_jit_decode_fused"]),
-    ("defines-cps3-wpb2-ahead-flat", {"LONGHAIR_AMD_JIT_DEFINES": "LH_CPS=3,LH_WPB=2,LH_WGCU=2,LH_CPS_AHEAD=1,LH_CPS_FLAT=1"},
-     ["lh_jit_decode_fused"]),
-    # the decode's memory-order form (slots read in multi-slot steps, each slot's network picked
-    # by its run-time row), with two step slots and with one (3 slots per step: partial last step)
-    ("defines-dmo", {"LONGHAIR_AMD_JIT_DEFINES": "LH_DMO=1"}, ["lh_jit_decode_fused"]),
-    ("defines-dmo-noahead-cps3", {"LONGHAIR_AMD_JIT_DEFINES": "LH_DMO=1,LH_DMO_AHEAD=0,LH_CPS=3"},
-     ["lh_jit_decode_fused"]),
+    ("defines-cps3-wpb2", {"LONGHAIR_AMD_JIT_DEFINES": "LH_CPS=3,LH_WPB=2,LH_WGCU=2"}, ["lh_jit_decode_fused"]),
 ]
 
 

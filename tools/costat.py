@@ -4,7 +4,7 @@
 counts, LDS bytes and code size from the code object's metadata.
 
 Usage: python tools/costat.py K M BYTES [enc|dec] [JIT_DEFINES]
-       e.g. python tools/costat.py 29 4 1296 dec LH_DMO=1"""
+       e.g. python tools/costat.py 29 4 1296 dec LH_LDG=3"""
 import glob
 import os
 import re

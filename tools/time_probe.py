@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Timing-only probe (no correctness check, for instrumented variants such as LH_PB_SKIP):
+"""Timing-only probe (no correctness check; for variants such as LONGHAIR_AMD_JIT_DEFINES=LH_LDG=3):
 encode_batch / decode_batch time per variant on a bench config.
 Usage: python tools/time_probe.py CONFIG 'NAME:ENV=VAL,ENV=VAL' ..."""
 import os

@@ -23,11 +23,8 @@ VARIANTS = [
     ("nofused", {"LONGHAIR_AMD_NO_FUSED_PLAN": "1"}),
 ]
 KNOBS = ["LONGHAIR_AMD_JIT_DEFINES", "LONGHAIR_AMD_NO_FUSED_PLAN"]
-# Large-m (windowed) variants: rows per wave and columns in flight.
-VARIANTS_WIN = [
-    ("base", {}),
-    ("pb_branch", {"LONGHAIR_AMD_JIT_DEFINES": "LH_PB_MASK=0"}),
-]
+# Large-m (windowed) modules: no standing variant (their knobs, LH_NT / LH_NT_R, via TUNE_VARIANTS).
+VARIANTS_WIN = [("base", {})]
 
 
 def main():
