@@ -118,3 +118,83 @@ def erasure_case(seed, k, m, e, shuffle=True):
         slots = [slots[i] for i in order]
     rows = [x if kind == "d" else k + x for kind, x in slots]
     return slots, rows
+
+
+# ------------------------------------------------------------------ invalid stripes
+# include/cauchy_256_batch.h: a stripe whose rows hold a duplicate or a row >= k + m is
+# invalid (status -1, left untouched).  `invalidate_rows` breaks a valid stripe in one named
+# way, `rows_valid` is that rule in plain Python (tests/test_lhutil_rows.py keeps the two in
+# step, so a GPU test never passes because its generator stopped producing invalid stripes).
+INVALID_KINDS = ("dup-orig", "dup-rec", "range", "range255")
+INVALID_WHERE = ("first", "last", "wave", "wave+1", "rand")
+
+
+def rows_valid(rows, k, m):
+    """The header's rule: all k rows distinct and every one < k + m."""
+    rows = [int(r) for r in rows]
+    return len(rows) == k and len(set(rows)) == k and all(0 <= r < k + m for r in rows)
+
+
+def invalid_kinds(k, m):
+    """The kinds of `invalidate_rows` that apply to a (k, m) code."""
+    kinds = []
+    if k >= 2:
+        kinds += ["dup-orig", "dup-rec"]
+    if k + m <= 255:
+        kinds += ["range", "range255"]
+    return kinds
+
+
+def invalid_pairs(k, m):
+    """Every (kind, where) pair that applies to the shape, ordered by diagonals so that any
+    run of len(kinds) consecutive pairs holds every kind once, at different positions."""
+    kinds = invalid_kinds(k, m)
+    n = len(INVALID_WHERE)
+    return [(kind, INVALID_WHERE[(i + d) % n]) for d in range(n) for i, kind in enumerate(kinds)]
+
+
+def invalidate_rows(rows, k, m, kind, where, rng):
+    """A copy of one stripe's valid row list (as `erasure_case` returns it) made invalid.
+
+    kind:  'dup-orig'  the slot takes the row of another slot that holds an original (when no
+                       other slot holds one: as 'dup-rec');
+           'dup-rec'   the slot takes the row of another slot that holds a recovery row (when
+                       there is none: the slot and one other both get row k);
+           'range'     the slot gets k + m;   'range255'  the slot gets 255 (both need
+                       k + m <= 255).
+    where: the slot overwritten: 'first' 0, 'last' k - 1, 'wave' 63 (k > 63, else k - 1),
+           'wave+1' 64 (k > 64, else 0), 'rand' a random slot.
+    Raises ValueError when the kind does not apply to the shape; never returns a valid stripe."""
+    rows = [int(r) for r in rows]
+    if not rows_valid(rows, k, m):
+        raise ValueError("invalidate_rows needs a valid stripe")
+    pos = {"first": 0, "last": k - 1, "wave": 63 if k > 63 else k - 1, "wave+1": 64 if k > 64 else 0,
+           "rand": None}
+    if where not in pos:
+        raise ValueError(f"unknown position {where!r}")
+    if kind not in INVALID_KINDS:
+        raise ValueError(f"unknown kind {kind!r}")
+    if kind not in invalid_kinds(k, m):
+        raise ValueError(f"kind {kind!r} does not apply to k = {k}, m = {m}")
+    p = pos[where] if pos[where] is not None else int(rng.integers(0, k))
+    out = list(rows)
+    others = [i for i in range(k) if i != p]
+    if kind == "dup-orig":
+        cand = [i for i in others if rows[i] < k]
+        if not cand:
+            kind = "dup-rec"
+    if kind == "dup-rec":
+        cand = [i for i in others if rows[i] >= k]
+    if kind in ("dup-orig", "dup-rec"):
+        if cand:
+            out[p] = rows[cand[int(rng.integers(0, len(cand)))]]
+        else:  # no recovery row anywhere else: two slots claim recovery row k
+            out[p] = k
+            out[others[int(rng.integers(0, len(others)))]] = k
+    elif kind == "range":
+        out[p] = k + m
+    else:
+        out[p] = 255
+    if rows_valid(out, k, m):
+        raise AssertionError(("invalidate_rows produced a valid stripe", rows, kind, where))
+    return out

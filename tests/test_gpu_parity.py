@@ -176,17 +176,29 @@ def test_dropin_concurrent_callers(lh, oracle, k, m, nbytes):
     assert not errors, errors
 
 
-def test_dropin_invalid_rows_untouched(lh, policy):
+@pytest.mark.parametrize("k,m,nbytes", [(6, 3, 16), (17, 6, 520), (9, 9, 64), (40, 20, 4096)])
+def test_dropin_invalid_rows_untouched(lh, policy, k, m, nbytes):
     """Duplicate or out-of-range rows: -1 and the blocks untouched (documented deviation:
-    undefined behaviour in the reference, cauchy_256.cpp:612-614, :733)."""
+    undefined behaviour in the reference, cauchy_256.cpp:612-614, :733).  A repeated recovery
+    row in the last two slots, a row = k + m in the last slot, and lhutil.invalidate_rows'
+    'dup-rec', 'range255' and a duplicate in the last slot on a random erasure pattern (e >= 2,
+    so a recovery row always remains: without one the call returns 0 before it looks at the
+    rows, the reference's own no-erasure rule, cauchy_256.cpp:1282-1284)."""
     codec = DropIn(lh)
-    k, m, nbytes = 6, 3, 16
-    for rows in ([0, 1, 2, 3, 6, 6], [0, 1, 2, 3, 4, 9]):
-        bufs = [lhutil.fill(i, nbytes) for i in range(k)]
+    rng = np.random.Generator(np.random.PCG64(k * 100 + m))
+    cases = [list(range(k - 2)) + [k, k], list(range(k - 1)) + [k + m]]
+    if (k, m) == (6, 3):
+        assert cases == [[0, 1, 2, 3, 6, 6], [0, 1, 2, 3, 4, 9]]
+    for kind, where in (("dup-rec", "rand"), ("range255", "rand"), ("dup-orig", "last"), ("dup-rec", "last")):
+        valid = lhutil.erasure_case(int(rng.integers(0, 2**31)), k, m, int(rng.integers(2, min(k, m))))[1]
+        cases.append(lhutil.invalidate_rows(valid, k, m, kind, where, rng))
+    for c, rows in enumerate(cases):
+        assert not lhutil.rows_valid(rows, k, m)
+        bufs = [lhutil.fill(c * 1000 + i, nbytes) for i in range(k)]
         before = [b.copy() for b in bufs]
         rc, got = codec.decode(k, m, bufs, rows, nbytes)
-        assert rc == -1 and got == rows
-        assert all(a.tobytes() == b.tobytes() for a, b in zip(bufs, before))
+        assert rc == -1 and got == rows, (rows, rc, got)
+        assert all(a.tobytes() == b.tobytes() for a, b in zip(bufs, before)), rows
 
 
 def test_dropin_auto_policy_routes_by_size(lh, oracle):
@@ -293,6 +305,35 @@ def test_dropin_device_pointers_invalid_size(lh):
     assert (got[1:] == 9).all()
 
 
+def test_dropin_device_pointers_invalid_rows(lh):
+    """All-device decode (policy gpu, the pointer-table form) with duplicate rows: -1, and the
+    Block.row values, every block and the pool bytes between the blocks are unchanged."""
+    import torch
+    k, m, nbytes = 29, 4, 1296
+    prev = lh.set_dispatch("gpu")
+    try:
+        rng = np.random.Generator(np.random.PCG64(29))
+        pool = torch.full(((k + 3) * (nbytes + 16),), 0xA5, dtype=torch.uint8, device="cuda")
+        off = [((i * 7919) % (k + 3)) * (nbytes + 16) + (i % 5) for i in range(k)]  # scattered, odd offsets
+        assert len({o // (nbytes + 16) for o in off}) == k
+        for i in range(k):
+            pool[off[i]:off[i] + nbytes] = torch.from_numpy(lhutil.fill(300 + i, nbytes)).cuda()
+        before = pool.cpu().numpy()
+        for kind, where in (("dup-orig", "rand"), ("dup-rec", "last"), ("dup-rec", "first")):
+            rows = lhutil.invalidate_rows(lhutil.erasure_case(7, k, m, 3)[1], k, m, kind, where, rng)
+            blocks = (lh.Block * k)()
+            for i in range(k):
+                blocks[i].data = ctypes.cast(pool.data_ptr() + off[i], ctypes.POINTER(ctypes.c_ubyte))
+                blocks[i].row = rows[i]
+            assert lh.cauchy_256_decode(k, m, blocks, nbytes) == -1, (kind, where)
+            assert any("(pointer table)" in n for n in lh.last_launch()), lh.last_launch()  # decoded in place
+            assert [blocks[i].row for i in range(k)] == rows, (kind, where)
+            torch.cuda.synchronize()
+            assert np.array_equal(pool.cpu().numpy(), before), (kind, where)  # blocks and the bytes between
+    finally:
+        lh.set_dispatch(prev)
+
+
 # ---------------------------------------------------------------- batched API
 
 
@@ -373,11 +414,13 @@ def _decode_batch_vs_oracle(lh, oracle, k, m, nbytes, stripes, e):
 def test_decode_batch_invalid_rows(lh):
     import torch
     k, m, nbytes = 6, 3, 16
-    blocks = torch.zeros((2, k, nbytes), dtype=torch.uint8, device="cuda")
+    filled = lhutil.fill(63, 2 * k * nbytes).reshape(2, k, nbytes)
+    blocks = _gpu_tensor(filled)
     rows = torch.tensor([[0, 1, 2, 3, 4, 4], [0, 1, 2, 3, 4, 9]], dtype=torch.uint8, device="cuda")
     status = lh.decode_batch(blocks, rows, m)
     assert status.cpu().tolist() == [-1, -1]
     assert rows.cpu().tolist() == [[0, 1, 2, 3, 4, 4], [0, 1, 2, 3, 4, 9]]
+    assert np.array_equal(blocks.cpu().numpy(), filled)
 
 
 def test_batch_invalid_params(lh):
@@ -525,6 +568,42 @@ def test_host_batch_padded_stride(lh, oracle, monkeypatch, writeback):
     assert rc == 0 and (status == 0).all()
     assert np.array_equal(pr, exp_rows)
     assert np.array_equal(view, exp)
+
+
+@pytest.mark.parametrize("pinned", [True, False], ids=["pinned", "pageable"])
+@pytest.mark.parametrize("writeback", ["kernel", "range"])
+def test_host_batch_invalid_stripes(lh, oracle, monkeypatch, writeback, pinned):
+    """The host-memory pipeline on a batch with invalid stripes (a quarter of 60, k17/m6/520,
+    16 stripes per chunk, a padded stride through the C call): valid stripes are the oracle's,
+    invalid ones keep their blocks and rows, status 0 / -1 accordingly, the pad bytes intact;
+    both write-back forms, pinned and pageable buffers."""
+    import torch
+    import test_gpu_untouched as tu
+    monkeypatch.setenv("LONGHAIR_AMD_PIPE_WRITEBACK", writeback)
+    k, m, nbytes, stripes, pad = 17, 6, 520, 60, 72
+    stride = k * nbytes + pad
+    blocks, rows, invalid, exp_blocks, exp_rows = tu.mixed_case(oracle, k, m, nbytes, stripes, 1706)
+    assert 4 <= int(invalid.sum()) <= stripes // 3 and invalid[0] and invalid[-1]
+
+    def host(arr):  # a writable copy, pinned or pageable
+        return torch.from_numpy(arr.copy()).pin_memory().numpy() if pinned else arr.copy()
+
+    raw = host(np.full(stripes * stride, 0xA5, dtype=np.uint8))
+    view = raw.reshape(stripes, stride)
+    view[:, :k * nbytes] = blocks.reshape(stripes, -1)
+    exp = view.copy()
+    exp[:, :k * nbytes] = exp_blocks.reshape(stripes, -1)
+    hr = host(rows)
+    status = np.full(stripes, 0x77, dtype=np.int8)
+    rc = lh.lib().cauchy_256_decode_host_batch(k, m, nbytes, stripes, raw.ctypes.data, stride, hr.ctypes.data,
+                                               status.ctypes.data, 16)
+    assert rc == 0, lh.lib().cauchy_256_last_error()
+    assert status.tolist() == [-1 if b else 0 for b in invalid]
+    bad_rows = [s for s in range(stripes) if hr[s].tolist() != exp_rows[s].tolist()]
+    assert not bad_rows, ("rows", bad_rows, invalid[bad_rows].tolist())
+    assert (view[:, k * nbytes:] == 0xA5).all(), "pad bytes written"
+    bad = [s for s in range(stripes) if view[s].tobytes() != exp[s].tobytes()]
+    assert not bad, ("blocks", bad, invalid[bad].tolist())
 
 
 # ------------------------------------------------------------------- packet framing

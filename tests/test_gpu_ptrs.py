@@ -10,6 +10,8 @@ launch trace shows which form ran: the specialised kernels reading the blocks in
 ("(pointer table)": the register networks, the windowed large-m kernels with the phase-B
 kernel, and for shapes without a specialised module the generic jump apply) or the gather /
 strided / scatter form (m = 1, k = 1, sub-blocks under 4 bytes, the lone-last-lane decode)."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -58,6 +60,20 @@ def _gather(pool, place):
     return out.reshape(S, n, B)
 
 
+def _gaps_untouched(pool, place):
+    """Every pool byte outside the scattered blocks still holds the 0xA5 fill: the bytes
+    between the blocks, the offset head before each block and the 64-byte tail of the pool."""
+    S, n, B, stride, order, offs = place
+    raw = pool.cpu().numpy()
+    gap = np.ones(raw.size, dtype=bool)
+    start = order * stride + offs
+    for b in start.tolist():
+        gap[b:b + B] = False
+    assert gap[S * n * stride:].all() and int(gap.sum()) == raw.size - S * n * B
+    bad = np.nonzero(gap & (raw != 0xA5))[0]
+    assert bad.size == 0, ("pool bytes outside the blocks were written", bad[:8].tolist(), "of", raw.size)
+
+
 ENCODE = [
     # (k, m, bytes, stripes, form)
     (29, 4, 1296, 300, "lh_jit_encode(pointer table)"),
@@ -81,7 +97,7 @@ def test_encode_batch_ptrs(lh, oracle, k, m, nbytes, stripes, form):
     g = torch.Generator(device="cuda").manual_seed(k * 1000 + m)
     data = torch.randint(0, 256, (stripes, k, nbytes), dtype=torch.uint8, device="cuda", generator=g)
     want = lh.encode_batch(data, m)
-    dpool, dptr, _ = _scatter(data, seed=k + m)
+    dpool, dptr, dplace = _scatter(data, seed=k + m)
     rpool, rptr, rplace = _scatter(torch.zeros((stripes, m, nbytes), dtype=torch.uint8, device="cuda"),
                                    seed=k * m + 1)
     lh.encode_batch_ptrs(k, m, nbytes, dptr, rptr)
@@ -89,6 +105,9 @@ def test_encode_batch_ptrs(lh, oracle, k, m, nbytes, stripes, form):
     assert form in lh.last_launch(), lh.last_launch()
     got = _gather(rpool, rplace)
     assert torch.equal(got, want)
+    _gaps_untouched(rpool, rplace)
+    assert torch.equal(_gather(dpool, dplace), data)   # the data blocks are only read
+    _gaps_untouched(dpool, dplace)
     host = data.cpu().numpy()
     for s in (0, stripes - 1):
         rc, rec = oracle.encode(k, m, host[s], nbytes)
@@ -102,7 +121,7 @@ def test_encode_batch_ptrs_invalid_writes_block0(lh):
     import torch
     k, m, nbytes, stripes = 5, 3, 12, 4
     data = torch.randint(0, 256, (stripes, k, nbytes), dtype=torch.uint8, device="cuda")
-    dpool, dptr, _ = _scatter(data, seed=3)
+    dpool, dptr, dplace = _scatter(data, seed=3)
     rpool, rptr, rplace = _scatter(torch.full((stripes, m, nbytes), 7, dtype=torch.uint8, device="cuda"), seed=4)
     with pytest.raises(lh.LonghairError):
         lh.encode_batch_ptrs(k, m, nbytes, dptr, rptr)
@@ -111,6 +130,8 @@ def test_encode_batch_ptrs_invalid_writes_block0(lh):
     x = np.bitwise_xor.reduce(data.cpu().numpy(), axis=1)
     assert (got[:, 0] == x).all()
     assert (got[:, 1:] == 7).all()
+    _gaps_untouched(rpool, rplace)
+    _gaps_untouched(dpool, dplace)
 
 
 DECODE = [
@@ -170,15 +191,89 @@ def test_decode_batch_ptrs(lh, oracle, k, m, nbytes, stripes, form):
     assert torch.equal(pstat, sstat)
     assert torch.equal(pr, sr)
     assert torch.equal(got, sb)
-    # and the oracle on a sample of stripes (stripe 1 may be the invalid one)
-    gh, gr = got.cpu().numpy(), pr.cpu().numpy()
-    for s in sorted({0, stripes - 1}):
-        bufs = [blocks[s, i].copy() for i in range(k)]
-        rc, exp_rows = oracle.decode(k, m, bufs, list(rows[s]), nbytes)
-        assert rc == 0
-        assert list(gr[s]) == exp_rows, s
-        for i in range(k):
-            assert gh[s, i].tobytes() == bufs[i].tobytes(), (s, i)
+    _gaps_untouched(pool, place)
+    # and the oracle on a sample of stripes; stripe 1, where it is the invalid one (m > 1 only:
+    # m = 1 accepts any rows), must hold what went in, with status -1
+    invalid1 = m > 1 and not lhutil.rows_valid(rows[1], k, m) if stripes >= 3 else False
+    assert invalid1 == (stripes >= 3 and k >= 2 and m > 1)
+
+    def check(got, got_rows):
+        gh, gr = got.cpu().numpy(), got_rows.cpu().numpy()
+        for s in sorted({0, stripes - 1}):
+            bufs = [blocks[s, i].copy() for i in range(k)]
+            rc, exp_rows = oracle.decode(k, m, bufs, list(rows[s]), nbytes)
+            assert rc == 0
+            assert list(gr[s]) == exp_rows, s
+            for i in range(k):
+                assert gh[s, i].tobytes() == bufs[i].tobytes(), (s, i)
+        if invalid1:
+            assert gr[1].tolist() == rows[1].tolist()
+            assert gh[1].tobytes() == blocks[1].tobytes()
+
+    check(got, pr)
+    st = pstat.cpu().numpy()
+    assert st.tolist() == [-1 if (invalid1 and s == 1) else 0 for s in range(stripes)]
+    # d_status = NULL (the header allows it) through the C call: the same blocks and rows
+    if (k, m, nbytes) in ((29, 4, 1296), (40, 20, 4096), (40, 20, 4104)):
+        pool2, ptrs2, place2 = _scatter(torch.from_numpy(blocks).cuda(), seed=k * 5 + m)
+        pr2 = torch.from_numpy(rows).cuda()
+        torch.cuda.synchronize()
+        rc = lh.lib().cauchy_256_decode_batch_ptrs(k, m, nbytes, stripes, ctypes.c_void_p(ptrs2.data_ptr()),
+                                                   ctypes.c_void_p(pr2.data_ptr()), None,
+                                                   ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        assert rc == 0, lh.lib().cauchy_256_last_error()
+        assert form in lh.last_launch(), lh.last_launch()
+        torch.cuda.synchronize()
+        got2 = _gather(pool2, place2)
+        assert torch.equal(pr2, sr) and torch.equal(got2, sb)
+        check(got2, pr2)
+        _gaps_untouched(pool2, place2)
+
+
+MIXED_PTRS = [
+    (29, 4, 1296, 50, "lh_jit_decode_fused(pointer table)"),
+    (29, 8, 1296, 24, "lh_jit_decode(pointer table)"),
+    (40, 20, 4096, 8, "lh_jit_decode_wide(pointer table)"),
+    (40, 20, 1024, 8, "lh_apply_jump_kernel(pointer table)"),
+    (40, 20, 4104, 8, "lh_ptr_copy_kernel(gather)"),
+    (40, 20, 24, 12, "lh_ptr_copy_kernel(gather)"),
+]
+
+
+@pytest.mark.parametrize("status", [True, False], ids=["status", "null-status"])
+@pytest.mark.parametrize("k,m,nbytes,stripes,form", MIXED_PTRS)
+def test_decode_batch_ptrs_mixed(lh, oracle, k, m, nbytes, stripes, form, status):
+    """Valid and invalid stripes in one pointer-table batch (test_gpu_untouched.mixed_case:
+    stripe 0, the last stripe, an adjacent pair and random others invalid, their blocks random
+    bytes), with a status array and with d_status = NULL: valid stripes are the oracle's,
+    invalid ones keep blocks and rows, the status is 0 / -1, and neither the pool outside the
+    blocks nor the guards around the rows and the status are written."""
+    import torch
+    import test_gpu_untouched as tu
+    blocks, rows, invalid, exp_blocks, exp_rows = tu.mixed_case(oracle, k, m, nbytes, stripes, k * 77 + m)
+    pool, ptrs, place = _scatter(torch.from_numpy(blocks.copy()).cuda(), seed=k + 5 * m)
+    gr = tu.Guarded(rows.reshape(1, stripes * k), 0, 0, tu.C_ROWS)
+    gs = tu.Guarded(np.full((1, stripes), tu.C_STATUS, dtype=np.uint8), 0, 0, tu.C_STATUS)
+    torch.cuda.synchronize()
+    rc = lh.lib().cauchy_256_decode_batch_ptrs(k, m, nbytes, stripes, ctypes.c_void_p(ptrs.data_ptr()),
+                                               ctypes.c_void_p(gr.ptr), ctypes.c_void_p(gs.ptr) if status else None,
+                                               ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert rc == 0, lh.lib().cauchy_256_last_error()
+    assert form in lh.last_launch(), lh.last_launch()
+    torch.cuda.synchronize()
+    got = _gather(pool, place).cpu().numpy()
+    got_rows = gr.check("rows").reshape(stripes, k)
+    got_status = gs.check("status").reshape(stripes)
+    for s in range(stripes):
+        what = ("invalid" if invalid[s] else "valid", "stripe", s, "rows in", rows[s].tolist())
+        assert got_rows[s].tolist() == exp_rows[s].tolist(), what
+        wrong = [i for i in range(k) if got[s, i].tobytes() != exp_blocks[s, i].tobytes()]
+        assert not wrong, (what, "slots", wrong)
+    if status:
+        assert got_status.view(np.int8).tolist() == [-1 if b else 0 for b in invalid]
+    else:
+        assert (got_status == tu.C_STATUS).all()
+    _gaps_untouched(pool, place)
 
 
 def test_decode_batch_ptrs_roundtrip_baseline_shape(lh):
@@ -220,12 +315,14 @@ def test_ptrs_gather_in_chunks(lh, oracle, monkeypatch, k, m, nbytes):
     monkeypatch.setenv("LONGHAIR_AMD_PTR_CHUNK_BYTES", str(3 * (k + m) * nbytes + 3 * k))
     data, blocks, rows = _received(lh, k, m, nbytes, stripes, seed=k + m)
     want = lh.encode_batch(data, m)
-    dpool, dptr, _ = _scatter(data, seed=5)
+    dpool, dptr, dplace = _scatter(data, seed=5)
     rpool, rptr, rplace = _scatter(torch.zeros((stripes, m, nbytes), dtype=torch.uint8, device="cuda"), seed=6)
     lh.encode_batch_ptrs(k, m, nbytes, dptr, rptr)
     torch.cuda.synchronize()
     assert lh.last_launch()[0] == "lh_ptr_copy_kernel(gather)", lh.last_launch()
     assert torch.equal(_gather(rpool, rplace), want)
+    _gaps_untouched(rpool, rplace)
+    _gaps_untouched(dpool, dplace)
     sb, sr = torch.from_numpy(blocks).cuda(), torch.from_numpy(rows).cuda()
     sstat = lh.decode_batch(sb, sr, m)
     pool, ptrs, place = _scatter(torch.from_numpy(blocks).cuda(), seed=7)
@@ -234,6 +331,7 @@ def test_ptrs_gather_in_chunks(lh, oracle, monkeypatch, k, m, nbytes):
     torch.cuda.synchronize()
     assert torch.equal(pstat, sstat) and torch.equal(pr, sr)
     assert torch.equal(_gather(pool, place), sb)
+    _gaps_untouched(pool, place)
 
 
 @pytest.mark.parametrize("k,m,nbytes", [(29, 4, 1296), (128, 32, 8192), (200, 3, 64)])
