@@ -331,22 +331,285 @@ static const JitKernels *jit_lookup(Device *d, const JitConfig &cfg, bool allow_
     return jk;
 }
 
-// ------------------------------------------------------------------------ encode
+// ---------------------------------------------------------------- blocks and routes
+static int check_shape(int k, int m, int bytes, int stripes) {
+    if (k < 1 || m < 1 || bytes <= 0 || stripes < 0 || k > 256 || m > 256)
+        return fail(kInvalid, "invalid k, m, block_bytes or stripes");
+    return kOk;
+}
+
+// Where a batch's blocks are.  Strided: block j of stripe s at p + s * stride + j * bytes.
+// Pointer table (cauchy_256_*_batch_ptrs; cauchy_256.h:78 data_ptrs[], :103 Block *): p is a
+// table in device memory whose row s holds stripe s's n block pointers, stride = n * 8 (the
+// row pitch).  The specialised kernels take exactly this pair in both forms.
+struct Blocks {
+    const void *p;
+    long long stride;
+    bool table;
+    uint8_t *bytes() const { return (uint8_t *)p; }
+    uint8_t *const *ptrs() const { return (uint8_t *const *)p; }
+};
+static Blocks strided_blocks(const void *p, long long stride) { return {p, stride, false}; }
+static Blocks table_blocks(uint8_t *const *ptrs, int n) { return {ptrs, (long long)n * 8, true}; }
+
+// The in / out side of the generic launchers' argument blocks (the other form's fields stay 0).
+static void set_in(JumpApplyArgs &a, const Blocks &b) {
+    if (b.table) {
+        a.in_ptrs = b.ptrs();
+        a.in_n = (int)(b.stride / 8);
+    } else {
+        a.in = b.bytes();
+        a.in_stride = b.stride;
+    }
+}
+static void set_out(JumpApplyArgs &a, const Blocks &b) {
+    if (b.table) {
+        a.out_ptrs = b.ptrs();
+        a.out_n = (int)(b.stride / 8);
+    } else {
+        a.out = b.bytes();
+        a.out_stride = b.stride;
+    }
+}
+static void set_blocks(InverseArgs &a, const Blocks &b) {
+    if (b.table) {
+        a.ptrs = b.ptrs();
+    } else {
+        a.blocks = b.bytes();
+        a.stride = b.stride;
+    }
+}
+
+// In place, with lanes of w sub-block bytes: the last lane of a sub-block -- shifted back over
+// its neighbour's bytes when w does not divide sub -- would sit alone in a workgroup of its own
+// (sub = 64 w t + 1 .. w - 1), without the barrier that orders its neighbour's reads before its
+// writes.
+static bool lone_tail(int sub, int w) {
+    const int nch = (sub + w - 1) / w;
+    return sub % w != 0 && nch > 1 && (nch - 1) % 64 == 0;
+}
+
+// The kernels that serve a batch call.  Both directions and both forms of Blocks share one
+// chain: register network -> its block-size family -> windowed -> jump apply -> bytewise
+// (strided) or gather / strided call / scatter (table).
+enum Path {
+    kPathXor,       // k = 1, m = 1, and block 0 of an invalid encode: lh_xor_reduce (strided only)
+    kPathRegister,  // lh_jit_encode; the planner, then lh_jit_decode
+    kPathFused,     // lh_jit_decode_fused: the plan computed inside the decode kernel
+    kPathWindowed,  // lh_jit_encode_win; the planner, lh_jit_decode_wide, phase B
+    kPathJump,      // the jump-table apply: flat (encode) or, after the planner, in place
+    kPathBytewise,  // tiny or lone-tail blocks: the generic apply (strided only)
+    kPathGather,    // no table form: gather, the strided call, scatter (table only)
+};
+struct Route {
+    Path path = kPathBytewise;
+    const JitKernels *jk = nullptr;  // kPathRegister, kPathFused, kPathWindowed
+    JitConfig cfg;                   // its configuration
+};
+
+// Routes a batch call whose shape passed check_shape (and, decoding, the k + m / bytes % 8
+// test).  `in`: the data blocks (encode) or the stripes' slots (decode).  kHipError when a
+// compilation made for this call (LONGHAIR_AMD_JIT_SYNC=1) failed.  Where the strided and the
+// table form, or the two directions, choose differently, one condition below says so.
+static int route(Device *d, bool decode, int k, int m, int bytes, const Blocks &in, bool allow_compile, Route *r) {
+    const bool tab = in.table;
+    if (k == 1 || m == 1 || k + m > 256 || bytes % 8 != 0) {
+        r->path = tab ? kPathGather : kPathXor;
+        return kOk;
+    }
+    std::string err;
+    bool hard = false;
+    // Strided only: the kernels read a wave's stripes through one buffer resource, whose 32-bit
+    // range must cover them (jit_codec.hip lh_encode_wave, lh_make_dsrc).
+    const bool reg = tab ? jit_ptr_config_for(k, m, bytes, decode, &r->cfg)
+                         : jit_config_for(k, m, bytes, decode, &r->cfg) &&
+                               in.stride * (r->cfg.spw ? r->cfg.spw : 1) < (1ll << 31);
+    if (reg) {
+        r->jk = jit_lookup(d, r->cfg, allow_compile, &err, &hard);
+        if (hard) return fail(kHipError, err);
+    }
+    // No size-specialised module yet (compiling in the background, or a drop-in call, which
+    // never compiles): the (k, m) block-size family's module, if loaded or cached (a batch call
+    // queues its compilation too).  Strided only; the encode asks only where the size-specialised
+    // configuration passed the range test above, the decode wherever it holds no module.
+    JitConfig fcfg;
+    if (!r->jk && !tab && (reg || decode) && !r->cfg.family && jit_family_config_for(k, m, bytes, &fcfg, decode) &&
+        in.stride * fcfg.spw < (1ll << 31)) {
+        std::string ferr;
+        bool fhard = false;
+        const JitKernels *fk = jit_lookup(d, fcfg, allow_compile, &ferr, &fhard);
+        if (fk && (decode ? fk->decode_fused : fk->encode)) {
+            r->jk = fk;
+            r->cfg = fcfg;
+        }
+    }
+    if (r->jk) {
+        const bool fused = decode && r->jk->decode_fused && std::getenv("LONGHAIR_AMD_NO_FUSED_PLAN") == nullptr;
+        r->path = fused ? kPathFused : kPathRegister;
+        return kOk;
+    }
+    // Windowed (large m, sub % (64 W) == 0).  The strided decode takes it whenever it holds no
+    // register-network module (one still compiling included), the table decode only for shapes
+    // without a register-network configuration at all.
+    if (!(decode && tab) || !jit_config_for(k, m, bytes, true, &r->cfg)) {
+        if (tab ? jit_win_ptr_config_for(k, m, bytes, &r->cfg, decode)
+                : jit_win_config_for(k, m, bytes, &r->cfg, decode)) {
+            const JitKernels *wk = jit_lookup(d, r->cfg, allow_compile, &err, &hard);
+            if (hard) return fail(kHipError, err);
+            if (wk && (decode ? wk->decode_wide : wk->encode_win)) {
+                r->jk = wk;
+                r->path = kPathWindowed;
+                return kOk;
+            }
+        }
+    }
+    // Generic: the jump-table apply (dword lanes, from sub = 4; in place unless lone_tail).
+    const int sub = bytes / 8;
+    r->path = sub >= 4 && !(decode && lone_tail(sub, 4)) ? kPathJump : tab ? kPathGather : kPathBytewise;
+    return kOk;
+}
+
+// Appends the configurations of the modules that serve (k, m, bytes) in one role, in compile
+// order: the strided form (register network, else windowed), the register network's block-size
+// family, the pointer-table form.
+enum { kFormStrided = 1, kFormFamily = 2, kFormTable = 4 };
+static void shape_configs(int k, int m, int bytes, bool decode, int forms, std::vector<JitConfig> *out) {
+    JitConfig cfg, c;
+    if (jit_config_for(k, m, bytes, decode, &cfg)) {
+        if (forms & kFormStrided) out->push_back(cfg);
+        if ((forms & kFormFamily) && !cfg.family && jit_family_config_for(k, m, bytes, &c, decode)) out->push_back(c);
+        if ((forms & kFormTable) && jit_ptr_config_for(k, m, bytes, decode, &c)) out->push_back(c);
+    } else if (jit_win_config_for(k, m, bytes, &cfg, decode)) {
+        if (forms & kFormStrided) out->push_back(cfg);
+        if ((forms & kFormTable) && jit_win_ptr_config_for(k, m, bytes, &c, decode)) out->push_back(c);
+    }
+}
+
+// ----------------------------------------------------------------------- launches
+// One helper per specialised kernel: its argument list, grid, block size, dynamic LDS, size
+// check and trace name.
+static void note_jit_launch(const char *kernel, const Route &r, const Blocks &b) {
+    char name[64];
+    std::snprintf(name, sizeof name, "%s%s", kernel, b.table ? "(pointer table)" : r.cfg.family ? "(family)" : "");
+    note_launch(name);
+}
+
+static int launch_jit_encode(const Route &r, int bytes, int stripes, Blocks in, Blocks out, hipStream_t st) {
+    // (table form: jit_ptr_config_for forces enc_wpb = 4, so this is jit_blocks and 256 threads)
+    long long blocks = jit_encode_blocks(r.cfg, stripes);
+    if (r.cfg.family) {  // (the family kernel takes the block size; spw follows from it)
+        const long long spw = 64 / ((bytes / 8 + 7) / 8);
+        blocks = ((stripes + spw - 1) / spw + r.cfg.enc_wpb - 1) / r.cfg.enc_wpb;
+    }
+    if (blocks > 0x7FFFFFFF) return fail(kInvalid, "batch too large");
+    int n = stripes, bb = bytes;  // (bb: the family kernel's last parameter; the others declare none)
+    void *args[] = {(void *)&in.p, &in.stride, (void *)&out.p, &out.stride, &n, &bb};
+    const unsigned lds = in.table ? 0 : r.jk->dyn_lds;  // (table form: none, even under an LH_WGCU= define)
+    LH_HIP(hipModuleLaunchKernel(r.jk->encode, (unsigned)blocks, 1, 1, 64u * (unsigned)r.cfg.enc_wpb, 1, 1, lds, st,
+                                 args, nullptr));
+    note_jit_launch("lh_jit_encode", r, in);
+    return kOk;
+}
+
+static int launch_jit_encode_win(const Route &r, int m, int bytes, int stripes, Blocks in, Blocks out, hipStream_t st) {
+    const long long blocks = (long long)stripes * (r.cfg.sub / (64 * r.cfg.W));
+    if (blocks > 0x7FFFFFFF) return fail(kInvalid, "batch too large");
+    const unsigned threads = 64u * (unsigned)((m + r.cfg.rows_per_wave - 1) / r.cfg.rows_per_wave);
+    int n = stripes, bb = bytes;  // (windowed modules take the block size as an argument)
+    void *args[] = {(void *)&in.p, &in.stride, (void *)&out.p, &out.stride, &n, &bb};
+    LH_HIP(hipModuleLaunchKernel(r.jk->encode_win, (unsigned)blocks, 1, 1, threads, 1, 1, 0, st, args, nullptr));
+    note_jit_launch("lh_jit_encode_win", r, in);
+    return kOk;
+}
+
+// Plan computed inside the decode kernel: one launch, no plan workspace.
+static int launch_jit_decode_fused(Device *d, const Route &r, int bytes, int stripes, Blocks blk, uint8_t *d_rows,
+                                   int8_t *d_status, hipStream_t st) {
+    // (4-wave workgroups: family and size-specialised modules alike)
+    const long long blocks = jit_blocks(r.cfg, stripes);
+    if (blocks > 0x7FFFFFFF) return fail(kInvalid, "batch too large");
+    const uint8_t *zero = nullptr;
+    if (int rc = zero_page(d, (size_t)bytes, &zero, st)) return rc;
+    const uint8_t *gexp = d->gf_exp;
+    const int16_t *glog = d->gf_log;
+    // (Stripes past the last whole round of resident waves on a prefetch-depth-3 copy of
+    // this kernel measured slower, 0.627 vs 0.610 ms at k29/m4 x 65 536: the partial round
+    // costs < 1 %, the second launch more; profiles/r3w_decode_tail.txt.)
+    // (bb: the family kernel's last parameter, cfg.spw follows it; the other kernels declare none)
+    int n = stripes, bb = bytes;
+    void *args[] = {(void *)&blk.p, &blk.stride, (void *)&d_rows, (void *)&d_status, (void *)&zero,
+                    (void *)&gexp, (void *)&glog, &n, &bb};
+    const unsigned lds = blk.table ? 0 : r.jk->dyn_lds;  // (table form: none, even under an LH_WGCU= define)
+    LH_HIP(hipModuleLaunchKernel(r.jk->decode_fused, (unsigned)blocks, 1, 1, 256, 1, 1, lds, st, args, nullptr));
+    note_jit_launch("lh_jit_decode_fused", r, blk);
+    return kOk;
+}
+
+// The stripes' plans are in w->plan (run_planner).
+static int launch_jit_decode(Device *d, const Route &r, int bytes, int stripes, Blocks blk, const Workspace *w,
+                             long long plan_stride, hipStream_t st) {
+    const long long blocks = jit_blocks(r.cfg, stripes);
+    if (blocks > 0x7FFFFFFF) return fail(kInvalid, "batch too large");
+    const uint8_t *zero = nullptr;
+    if (int rc = zero_page(d, (size_t)bytes, &zero, st)) return rc;
+    const uint8_t *plan = w->plan.ptr;
+    int n = stripes;
+    void *args[] = {(void *)&blk.p, &blk.stride, (void *)&plan, &plan_stride, (void *)&zero, &n};
+    LH_HIP(hipModuleLaunchKernel(r.jk->decode, (unsigned)blocks, 1, 1, 256, 1, 1, 0, st, args, nullptr));
+    note_jit_launch("lh_jit_decode", r, blk);
+    return kOk;
+}
+
+// The plan workspace holds the stripes' plans, then (16-byte aligned) one int per stripe:
+// phase B's launch order (InverseArgs::order).
+static size_t plan_order_offset(int stripes, long long plan_stride) {
+    return ((size_t)stripes * (size_t)plan_stride + 15) & ~(size_t)15;
+}
+static size_t plan_workspace_bytes(int k, int m, int e_max, int stripes) {
+    return plan_order_offset(stripes, PlanView::bytes(k, m, e_max)) + (size_t)stripes * sizeof(int);
+}
+
+// Large m (<= 64), sub % (64 W) == 0, after the planner: the windowed phase-A kernel
+// lh_jit_decode_wide (V_r in place of R_r), then lh_inverse_gt_kernel (phase B), both over the
+// whole batch.  (Round 3 also ran them per chunk of stripes, so a chunk's V could be read back
+// from the Infinity Cache, optionally with phase B on a side stream: slower at every chunk
+// size, profiles/r3c_wide_chunk.txt; removed in round 5.)
+static int launch_jit_decode_wide(Device *d, const Route &r, int k, int m, int e_max, int bytes, int stripes,
+                                  Blocks blk, const Workspace *w, long long plan_stride, hipStream_t st) {
+    const long long blocks = (long long)stripes * (r.cfg.sub / (64 * r.cfg.W));
+    if (blocks > 0x7FFFFFFF) return fail(kInvalid, "batch too large");
+    const uint8_t *zero = nullptr;
+    if (int rc = zero_page(d, (size_t)bytes, &zero, st)) return rc;
+    const unsigned threads = 64u * (unsigned)((m + r.cfg.rows_per_wave - 1) / r.cfg.rows_per_wave);
+    const uint8_t *plan = w->plan.ptr;
+    int n = stripes, bb = bytes;  // (windowed modules take the block size as an argument)
+    void *args[] = {(void *)&blk.p, &blk.stride, (void *)&plan, &plan_stride, (void *)&zero, &n, &bb};
+    LH_HIP(hipModuleLaunchKernel(r.jk->decode_wide, (unsigned)blocks, 1, 1, threads, 1, 1, 0, st, args, nullptr));
+    note_jit_launch("lh_jit_decode_wide", r, blk);
+    InverseArgs ia{};  // phase A left V_r in the recovery slots: phase B
+    set_blocks(ia, blk);
+    ia.plan = plan;
+    ia.plan_stride = plan_stride;
+    ia.k = k;
+    ia.m = m;
+    ia.e_max = e_max;
+    ia.bytes = bytes;
+    ia.stripes = stripes;
+    ia.order = (int *)(w->plan.ptr + plan_order_offset(stripes, plan_stride));
+    LH_HIP(launch_inverse(ia, st));
+    return kOk;
+}
+
 // The jump-table apply's lane width (a.sub, a.n_out, a.per_stripe set): two-dword lanes
 // (lh_apply_jump2_kernel: a jump covers 8 bytes per lane) only where a one-dword wave would be
 // half empty -- at most 4 outputs -- and the lanes stay full: a flat (encode) launch with
 // sub >= 8, an in-place decode with sub >= 512.  With more outputs the one-dword form wins
 // (its wave carries 8 outputs per jump target fetch; profiles/r5f_jump_dw.txt: k128/m32
 // encode 5.31 ms one-dword, 8.27 two-dword; k29/m4 encode 0.700 / 0.665).  In place, the last
-// lane of a sub-block (shifted back over its neighbour when the width does not divide sub)
-// must share its neighbour's workgroup, whose barrier orders every read of a slot before its
-// overwrite.
+// lane of a sub-block must share its neighbour's workgroup, whose barrier orders every read
+// of a slot before its overwrite (lone_tail).
 static void jump_layout(const Device *d, JumpApplyArgs &a, bool in_place) {
-    auto lone_tail = [&](int w) {
-        const int nch = (a.sub + w - 1) / w;
-        return a.sub % w != 0 && nch > 1 && (nch - 1) % 64 == 0;
-    };
-    bool two = a.n_out <= 4 && a.sub >= 8 && (!in_place || (a.sub >= 512 && !lone_tail(8)));
+    bool two = a.n_out <= 4 && a.sub >= 8 && (!in_place || (a.sub >= 512 && !lone_tail(a.sub, 8)));
     const char *fb = std::getenv("LONGHAIR_AMD_INV_FALLBACK");  // (tests: the in-asm table)
     if (fb && std::atoi(fb)) two = false;
     a.dw = two && d->jump2 ? 2 : 1;
@@ -354,6 +617,34 @@ static void jump_layout(const Device *d, JumpApplyArgs &a, bool in_place) {
     a.wps = (a.nch + 63) / 64;
 }
 
+// The generic jump-table apply.  w == nullptr: the flat encode, out = G x in.  Else the decode
+// in place (out == in) by the stripes' plans in w->plan (run_planner with want_w).
+static int launch_jump(Device *d, int k, int m, int bytes, int stripes, Blocks in, Blocks out, const Workspace *w,
+                       hipStream_t st) {
+    JumpApplyArgs a{};
+    set_in(a, in);
+    set_out(a, out);
+    a.n_in = k;
+    a.n_out = m;
+    a.bytes = bytes;
+    a.sub = bytes / 8;
+    a.stripes = stripes;
+    if (w) {
+        a.n_out = k < m ? k : m;
+        a.plan_stride = a.coef_stride = PlanView::bytes(k, m, a.n_out);
+        a.plan = w->plan.ptr;
+        a.coef = w->plan.ptr + PlanView::w_offset(k, m, a.n_out);
+        a.per_stripe = 1;
+        a.order = (int *)(w->plan.ptr + plan_order_offset(stripes, a.plan_stride));  // by e, largest first
+    } else if (int rc = device_generator(d, k, m, &a.coef, nullptr, st)) {
+        return rc;
+    }
+    jump_layout(d, a, w != nullptr);
+    LH_HIP(launch_apply_jump(a, st));
+    return kOk;
+}
+
+// ------------------------------------------------------------------------ encode
 static int xor_rows(int k, int n_rep, int bytes, int stripes, const uint8_t *in, long long in_stride,
                     uint8_t *out, long long out_stride, hipStream_t st) {
     XorArgs a{};
@@ -373,103 +664,33 @@ static int xor_rows(int k, int n_rep, int bytes, int stripes, const uint8_t *in,
 
 static int encode_batch(int k, int m, int bytes, int stripes, const uint8_t *d_data, long long data_stride,
                         uint8_t *d_rec, long long rec_stride, hipStream_t st, bool allow_compile) {
-    if (k < 1 || m < 1 || bytes <= 0 || stripes < 0 || k > 256 || m > 256)
-        return fail(kInvalid, "invalid k, m, block_bytes or stripes");
+    if (int rc = check_shape(k, m, bytes, stripes)) return rc;
     if (stripes == 0) return kOk;
     if (data_stride < (long long)k * bytes || rec_stride < (long long)m * bytes)
         return fail(kInvalid, "stripe strides smaller than the stripe");
     Device *d = nullptr;
     if (int rc = current_device(&d)) return rc;
-
-    if (k == 1) return xor_rows(1, m, bytes, stripes, d_data, data_stride, d_rec, rec_stride, st);
-    if (m == 1 || k + m > 256 || bytes % 8 != 0) {
+    const Blocks in = strided_blocks(d_data, data_stride), out = strided_blocks(d_rec, rec_stride);
+    Route r;
+    if (int rc = route(d, false, k, m, bytes, in, allow_compile, &r)) return rc;
+    switch (r.path) {
+    case kPathXor: {
+        if (k == 1) return xor_rows(1, m, bytes, stripes, d_data, data_stride, d_rec, rec_stride, st);
         // Recovery block 0 first, as the reference (cauchy_256.cpp:1511-1527).
         if (int rc = xor_rows(k, 1, bytes, stripes, d_data, data_stride, d_rec, rec_stride, st)) return rc;
         return m == 1 ? kOk : fail(kInvalid, "k + m > 256 or block_bytes % 8 != 0");
     }
-
-    JitConfig cfg;
-    // (the specialised encode reads a wave's stripes through one buffer resource, whose
-    // 32-bit range must cover them: jit_codec.hip lh_encode_wave)
-    if (jit_config_for(k, m, bytes, false, &cfg) && data_stride * (cfg.spw ? cfg.spw : 1) < (1ll << 31)) {
-        std::string err;
-        bool hard = false;
-        const JitKernels *jk = jit_lookup(d, cfg, allow_compile, &err, &hard);
-        // No size-specialised module yet (compiling in the background, or a drop-in call, which
-        // never compiles): the (k, m) block-size family's module, if loaded or cached (a batch
-        // call queues its compilation too).
-        JitConfig fcfg;
-        if (!jk && !hard && !cfg.family && jit_family_config_for(k, m, bytes, &fcfg) &&
-            data_stride * fcfg.spw < (1ll << 31)) {
-            std::string ferr;
-            bool fhard = false;
-            if (const JitKernels *fk = jit_lookup(d, fcfg, allow_compile, &ferr, &fhard)) {
-                jk = fk;
-                cfg = fcfg;
-            }
-        }
-        if (jk) {
-            long long blocks = jit_encode_blocks(cfg, stripes);
-            int bb = bytes;
-            if (cfg.family) {  // (the family kernel takes the block size; spw follows from it)
-                const long long spw = 64 / ((bytes / 8 + 7) / 8);
-                blocks = ((stripes + spw - 1) / spw + cfg.enc_wpb - 1) / cfg.enc_wpb;
-            }
-            if (blocks > 0x7FFFFFFF) return fail(kInvalid, "batch too large");
-            long long in_stride = data_stride, out_stride = rec_stride;
-            int n = stripes;
-            void *args[] = {(void *)&d_data, &in_stride, (void *)&d_rec, &out_stride, &n, &bb};
-            LH_HIP(hipModuleLaunchKernel(jk->encode, (unsigned)blocks, 1, 1, 64u * (unsigned)cfg.enc_wpb,
-                                         1, 1, jk->dyn_lds, st, args, nullptr));
-            note_launch(cfg.family ? "lh_jit_encode(family)" : "lh_jit_encode");
-            return kOk;
-        }
-        if (hard) return fail(kHipError, err);
+    case kPathRegister: return launch_jit_encode(r, bytes, stripes, in, out, st);
+    case kPathWindowed: return launch_jit_encode_win(r, m, bytes, stripes, in, out, st);
+    case kPathJump: return launch_jump(d, k, m, bytes, stripes, in, out, nullptr, st);
+    default: break;
     }
-    if (jit_win_config_for(k, m, bytes, &cfg)) {
-        std::string err;
-        bool hard = false;
-        const JitKernels *jk = jit_lookup(d, cfg, allow_compile, &err, &hard);
-        if (jk && jk->encode_win) {
-            const long long blocks = (long long)stripes * (cfg.sub / (64 * cfg.W));
-            if (blocks > 0x7FFFFFFF) return fail(kInvalid, "batch too large");
-            const unsigned threads = 64u * (unsigned)((m + cfg.rows_per_wave - 1) / cfg.rows_per_wave);
-            long long in_stride = data_stride, out_stride = rec_stride;
-            int n = stripes;
-            int bb = bytes;  // (windowed modules take the block size as an argument)
-            void *args[] = {(void *)&d_data, &in_stride, (void *)&d_rec, &out_stride, &n, &bb};
-            LH_HIP(hipModuleLaunchKernel(jk->encode_win, (unsigned)blocks, 1, 1, threads, 1, 1, 0, st, args, nullptr));
-            note_launch("lh_jit_encode_win");
-            return kOk;
-        }
-        if (hard) return fail(kHipError, err);
-    }
-    const uint8_t *G = nullptr;
-    if (int rc = device_generator(d, k, m, &G, nullptr, st)) return rc;
-    if (bytes / 8 >= 4) {  // the jump-table apply (dword lanes)
-        JumpApplyArgs a{};
-        a.in = d_data;
-        a.in_stride = data_stride;
-        a.out = d_rec;
-        a.out_stride = rec_stride;
-        a.coef = G;
-        a.coef_stride = 0;
-        a.n_in = k;
-        a.n_out = m;
-        a.bytes = bytes;
-        a.sub = bytes / 8;
-        a.stripes = stripes;
-        a.per_stripe = 0;
-        jump_layout(d, a, false);
-        LH_HIP(launch_apply_jump(a, st));
-        return kOk;
-    }
-    ApplyArgs a{};
+    ApplyArgs a{};  // kPathBytewise
+    if (int rc = device_generator(d, k, m, &a.coef, nullptr, st)) return rc;
     a.in = d_data;
     a.in_stride = data_stride;
     a.out = d_rec;
     a.out_stride = rec_stride;
-    a.coef = G;
     a.coef_stride = 0;
     a.n_in = k;
     a.n_out = m;
@@ -486,25 +707,17 @@ static int encode_batch(int k, int m, int bytes, int stripes, const uint8_t *d_d
 // The per-stripe erasure planner (lh_plan_kernel / lh_plan_small_kernel) into the stream's
 // plan workspace (reserved with `work_bytes` of generic-path workspace beside it).
 // LONGHAIR_AMD_PLAN_GJ (knob): Gauss-Jordan even where the closed form applies.
-// The plan workspace holds the stripes' plans, then (16-byte aligned) one int per stripe:
-// phase B's launch order (InverseArgs::order).
-static size_t plan_order_offset(int stripes, long long plan_stride) {
-    return ((size_t)stripes * (size_t)plan_stride + 15) & ~(size_t)15;
-}
-
 static int run_planner(Device *d, hipStream_t st, int k, int m, int e_max, int stripes, uint8_t *d_rows,
                        int8_t *d_status, size_t work_bytes, bool want_w, Workspace **out) {
-    const long long plan_stride = PlanView::bytes(k, m, e_max);
     Workspace *w = nullptr;
-    if (int rc = workspace(d, st, plan_order_offset(stripes, plan_stride) + (size_t)stripes * sizeof(int), work_bytes, &w))
-        return rc;
+    if (int rc = workspace(d, st, plan_workspace_bytes(k, m, e_max, stripes), work_bytes, &w)) return rc;
     const uint8_t *G = nullptr, *points = nullptr;
     if (int rc = device_generator(d, k, m, &G, &points, st)) return rc;
     PlanArgs pa{};
     pa.rows = d_rows;
     pa.status = d_status;
     pa.plan = w->plan.ptr;
-    pa.plan_stride = plan_stride;
+    pa.plan_stride = PlanView::bytes(k, m, e_max);
     pa.G = G;
     pa.points = std::getenv("LONGHAIR_AMD_PLAN_GJ") ? nullptr : points;
     pa.gf_exp = d->gf_exp;
@@ -521,87 +734,29 @@ static int run_planner(Device *d, hipStream_t st, int k, int m, int e_max, int s
 
 static int decode_batch(int k, int m, int bytes, int stripes, uint8_t *d_blocks, long long stride,
                         uint8_t *d_rows, int8_t *d_status, hipStream_t st, bool allow_compile) {
-    if (k < 1 || m < 1 || bytes <= 0 || stripes < 0 || k > 256 || m > 256)
-        return fail(kInvalid, "invalid k, m, block_bytes or stripes");
+    if (int rc = check_shape(k, m, bytes, stripes)) return rc;
     if (stripes == 0) return kOk;
     if (stride < (long long)k * bytes) return fail(kInvalid, "stripe stride smaller than the stripe");
     if (m > 1 && k > 1 && (k + m > 256 || bytes % 8 != 0))
         return fail(kInvalid, "k + m > 256 or block_bytes % 8 != 0");
     Device *d = nullptr;
     if (int rc = current_device(&d)) return rc;
+    const Blocks blk = strided_blocks(d_blocks, stride);
+    Route r;
+    if (int rc = route(d, true, k, m, bytes, blk, allow_compile, &r)) return rc;
+    if (r.path == kPathFused) return launch_jit_decode_fused(d, r, bytes, stripes, blk, d_rows, d_status, st);
 
     const int e_max = (m == 1 || k <= 1) ? 1 : (k < m ? k : m);
     const long long plan_stride = PlanView::bytes(k, m, e_max);
-    JitConfig cfg;
-    // The specialised decode reads a wave's stripes through one buffer resource, whose
-    // 32-bit range must cover them (jit_codec.hip lh_make_dsrc).
-    const bool jit_ok = (k > 1 && m > 1) && jit_config_for(k, m, bytes, true, &cfg) &&
-                        stride * (cfg.spw ? cfg.spw : 1) < (1ll << 31);
-    const JitKernels *jk = nullptr;
-    std::string err;
-    if (jit_ok) {
-        bool hard = false;
-        jk = jit_lookup(d, cfg, allow_compile, &err, &hard);
-        if (hard) return fail(kHipError, err);
-    }
-    // No size-specialised module yet (compiling in the background, or a drop-in call, which
-    // never compiles): the (k, m) block-size family's fused decode, if loaded or cached (a batch
-    // call queues its compilation too), as encode_batch does.
-    JitConfig fcfg;
-    if (!jk && k > 1 && m > 1 && !cfg.family && jit_family_config_for(k, m, bytes, &fcfg, true) &&
-        stride * fcfg.spw < (1ll << 31)) {
-        std::string ferr;
-        bool fhard = false;
-        if (const JitKernels *fk = jit_lookup(d, fcfg, allow_compile, &ferr, &fhard)) {
-            if (fk->decode_fused) {
-                jk = fk;
-                cfg = fcfg;
-            }
-        }
-    }
-    const bool generic = (k > 1 && m > 1) && !jk;
-    if (jk && jk->decode_fused && std::getenv("LONGHAIR_AMD_NO_FUSED_PLAN") == nullptr) {
-        // Plan computed inside the decode kernel: one launch, no plan workspace.
-        const uint8_t *zero = nullptr;
-        if (int rc = zero_page(d, (size_t)bytes, &zero, st)) return rc;
-        hipFunction_t fn = jk->decode_fused;
-        long long s1 = stride;
-        const uint8_t *gexp = d->gf_exp;
-        const int16_t *glog = d->gf_log;
-        // (Stripes past the last whole round of resident waves on a prefetch-depth-3 copy of
-        // this kernel measured slower, 0.627 vs 0.610 ms at k29/m4 x 65 536: the partial round
-        // costs < 1 %, the second launch more; profiles/r3w_decode_tail.txt.)
-        int n = stripes, bb = bytes;  // (bb: the family kernel's block-size argument; cfg.spw follows it)
-        void *args[] = {(void *)&d_blocks, &s1, (void *)&d_rows, (void *)&d_status, (void *)&zero,
-                        (void *)&gexp, (void *)&glog, &n, &bb};
-        // (4-wave workgroups: family and size-specialised modules alike)
-        LH_HIP(hipModuleLaunchKernel(fn, (unsigned)jit_blocks(cfg, stripes), 1, 1, 256, 1, 1, jk->dyn_lds, st, args,
-                                     nullptr));
-        note_launch(cfg.family ? "lh_jit_decode_fused(family)" : "lh_jit_decode_fused");
-        return kOk;
-    }
-    // Large m (<= 64), sub % (64 W) == 0, after the planner: the windowed phase-A kernel
-    // lh_jit_decode_wide (V_r in place of R_r), then lh_inverse_gt_kernel (phase B).
-    JitConfig wcfg;
-    const JitKernels *wk = nullptr;
-    if (generic && jit_win_config_for(k, m, bytes, &wcfg, true)) {
-        bool hard = false;
-        wk = jit_lookup(d, wcfg, allow_compile, &err, &hard);
-        if (hard) return fail(kHipError, err);
-        if (wk && !wk->decode_wide) wk = nullptr;
-    }
-    // The generic decode: the jump-table apply in place (dword lanes), unless the last dword
-    // lane of a sub-block -- shifted back over its neighbour's bytes when sub % 4 != 0 -- would
-    // sit alone in a workgroup of its own (sub = 256 t + 1..3): then the old apply into a
-    // workspace and a scatter.
-    const int sub = bytes / 8, jnch = (sub + 3) / 4;
-    const bool jump = generic && !wk && sub >= 4 && !(sub % 4 != 0 && jnch > 1 && (jnch - 1) % 64 == 0);
-    const size_t work_bytes = (generic && !wk && !jump) ? (size_t)stripes * e_max * bytes : 0;
+    // The generic paths apply the planner's W; the bytewise one writes the recovered originals
+    // into a workspace first.
+    const bool want_w = r.path == kPathJump || r.path == kPathBytewise;
+    const size_t work_bytes = r.path == kPathBytewise ? (size_t)stripes * e_max * bytes : 0;
     Workspace *w = nullptr;
-    if (int rc = run_planner(d, st, k, m, e_max, stripes, d_rows, d_status, work_bytes, generic && !wk, &w)) return rc;
-    if (k <= 1) return kOk;
-
-    if (m == 1) {
+    if (int rc = run_planner(d, st, k, m, e_max, stripes, d_rows, d_status, work_bytes, want_w, &w)) return rc;
+    switch (r.path) {
+    case kPathXor: {
+        if (k <= 1) return kOk;
         XorArgs a{};
         a.in = d_blocks;
         a.in_stride = stride;
@@ -620,74 +775,12 @@ static int decode_batch(int k, int m, int bytes, int stripes, uint8_t *d_blocks,
         LH_HIP(launch_xor_reduce(a, st));
         return kOk;
     }
-    if (jk) {
-        const uint8_t *zero = nullptr;
-        if (int rc = zero_page(d, (size_t)bytes, &zero, st)) return rc;
-        const long long blocks = jit_blocks(cfg, stripes);
-        long long s1 = stride, s2 = plan_stride;
-        const uint8_t *plan = w->plan.ptr;
-        int n = stripes;
-        void *args[] = {(void *)&d_blocks, &s1, (void *)&plan, &s2, (void *)&zero, &n};
-        LH_HIP(hipModuleLaunchKernel(jk->decode, (unsigned)blocks, 1, 1, 256, 1, 1, 0, st, args, nullptr));
-        note_launch("lh_jit_decode");
-        return kOk;
+    case kPathRegister: return launch_jit_decode(d, r, bytes, stripes, blk, w, plan_stride, st);
+    case kPathWindowed: return launch_jit_decode_wide(d, r, k, m, e_max, bytes, stripes, blk, w, plan_stride, st);
+    case kPathJump: return launch_jump(d, k, m, bytes, stripes, blk, blk, w, st);
+    default: break;
     }
-    if (wk) {
-        const uint8_t *zero = nullptr;
-        if (int rc = zero_page(d, (size_t)bytes, &zero, st)) return rc;
-        const long long cps = wcfg.sub / (64 * wcfg.W);
-        if ((long long)stripes * cps > 0x7FFFFFFF) return fail(kInvalid, "batch too large");
-        const unsigned threads = 64u * (unsigned)((m + wcfg.rows_per_wave - 1) / wcfg.rows_per_wave);
-        // Phase A then phase B over the whole batch.  (Round 3 also ran them per chunk of
-        // stripes, so a chunk's V could be read back from the Infinity Cache, optionally with
-        // phase B on a side stream: slower at every chunk size, profiles/r3c_wide_chunk.txt;
-        // removed in round 5.)
-        {
-            long long s1 = stride, s2 = plan_stride;
-            const uint8_t *plan = w->plan.ptr;
-            int nn = stripes;
-            int bb = bytes;  // (windowed modules take the block size as an argument)
-            void *args[] = {(void *)&d_blocks, &s1, (void *)&plan, &s2, (void *)&zero, &nn, &bb};
-            LH_HIP(hipModuleLaunchKernel(wk->decode_wide, (unsigned)(stripes * cps), 1, 1, threads, 1, 1, 0, st, args,
-                                         nullptr));
-            note_launch("lh_jit_decode_wide");
-            InverseArgs ia{};  // phase A left V_r in the recovery slots: phase B
-            ia.blocks = d_blocks;
-            ia.stride = stride;
-            ia.plan = plan;
-            ia.plan_stride = plan_stride;
-            ia.k = k;
-            ia.m = m;
-            ia.e_max = e_max;
-            ia.bytes = bytes;
-            ia.stripes = stripes;
-            ia.order = (int *)(w->plan.ptr + plan_order_offset(stripes, plan_stride));
-            LH_HIP(launch_inverse(ia, st));
-        }
-        return kOk;
-    }
-    if (jump) {
-        JumpApplyArgs a{};
-        a.in = d_blocks;
-        a.in_stride = stride;
-        a.out = d_blocks;
-        a.out_stride = stride;
-        a.coef = w->plan.ptr + PlanView::w_offset(k, m, e_max);
-        a.coef_stride = plan_stride;
-        a.plan = w->plan.ptr;
-        a.plan_stride = plan_stride;
-        a.n_in = k;
-        a.n_out = e_max;
-        a.bytes = bytes;
-        a.sub = sub;
-        a.stripes = stripes;
-        a.per_stripe = 1;
-        a.order = (int *)(w->plan.ptr + plan_order_offset(stripes, plan_stride));  // by e, largest first
-        jump_layout(d, a, true);
-        LH_HIP(launch_apply_jump(a, st));
-        return kOk;
-    }
-    // Generic, tiny blocks: recovered originals into the workspace, then into their slots.
+    // kPathBytewise: recovered originals into the workspace (the old apply), then into their slots.
     ApplyArgs a{};
     a.in = d_blocks;
     a.in_stride = stride;
@@ -722,13 +815,12 @@ static int decode_batch(int k, int m, int bytes, int stripes, uint8_t *d_blocks,
 }
 
 // ------------------------------------------------------------ pointer-table batches
-// The reference's per-block pointers (cauchy_256.h:78 data_ptrs[], :103 Block *) for a batch
-// of stripes, with the pointer tables in device memory: row s of a table holds stripe s's
-// block pointers.  Shapes with a register network (jit.cpp jit_ptr_config_for: the k29/m4
-// family) read and write the blocks where they lie (jit_codec.hip LH_PTR: a wave's table rows
-// staged in LDS).  Every other shape gathers each chunk of stripes into the stream's
-// workspace (lh_ptr_copy_kernel), runs the strided batch path on it and scatters the outputs
-// back: one extra read and write of the inputs, bit-identical results.
+// Routes with a table form (route) read and write the blocks where they lie: the register
+// networks (jit.cpp jit_ptr_config_for; jit_codec.hip LH_PTR: a wave's table rows staged in
+// LDS), the windowed modules and the jump-table apply.  Every other route (kPathGather)
+// gathers each chunk of stripes into the stream's workspace (lh_ptr_copy_kernel), runs the
+// strided batch path on it and scatters the outputs back: one extra read and write of the
+// inputs, bit-identical results.
 static constexpr long long kPtrChunkBytes = 256ll << 20;
 
 static int gather_chunk(Device *d, hipStream_t st, long long per_stripe, int stripes, uint8_t **buf, int *chunk) {
@@ -767,72 +859,23 @@ static int ptr_copy(uint8_t *const *ptrs, int n, int ncopy, uint8_t *chunk, long
 
 static int encode_batch_ptrs(int k, int m, int bytes, int stripes, uint8_t *const *data_ptrs, uint8_t *const *rec_ptrs,
                              hipStream_t st, bool allow_compile = true) {
-    if (k < 1 || m < 1 || bytes <= 0 || stripes < 0 || k > 256 || m > 256)
-        return fail(kInvalid, "invalid k, m, block_bytes or stripes");
+    if (int rc = check_shape(k, m, bytes, stripes)) return rc;
     if (stripes == 0) return kOk;
     if (!data_ptrs || !rec_ptrs) return fail(kInvalid, "null pointer table");
     Device *d = nullptr;
     if (int rc = current_device(&d)) return rc;
-    JitConfig cfg;
-    if (jit_ptr_config_for(k, m, bytes, false, &cfg)) {
-        std::string err;
-        bool hard = false;
-        const JitKernels *jk = jit_lookup(d, cfg, allow_compile, &err, &hard);
-        if (jk) {
-            const long long blocks = jit_blocks(cfg, stripes);
-            if (blocks > 0x7FFFFFFF) return fail(kInvalid, "batch too large");
-            long long in_stride = (long long)k * 8, out_stride = (long long)m * 8;
-            int n = stripes;
-            void *args[] = {(void *)&data_ptrs, &in_stride, (void *)&rec_ptrs, &out_stride, &n};
-            LH_HIP(hipModuleLaunchKernel(jk->encode, (unsigned)blocks, 1, 1, 256, 1, 1, 0, st, args, nullptr));
-            note_launch("lh_jit_encode(pointer table)");
-            return kOk;
-        }
-        if (hard) return fail(kHipError, err);
+    const Blocks in = table_blocks(data_ptrs, k), out = table_blocks(rec_ptrs, m);
+    Route r;
+    if (int rc = route(d, false, k, m, bytes, in, allow_compile, &r)) return rc;
+    switch (r.path) {
+    case kPathRegister: return launch_jit_encode(r, bytes, stripes, in, out, st);
+    case kPathWindowed: return launch_jit_encode_win(r, m, bytes, stripes, in, out, st);
+    case kPathJump: return launch_jump(d, k, m, bytes, stripes, in, out, nullptr, st);
+    default: break;
     }
-    if (jit_win_ptr_config_for(k, m, bytes, &cfg)) {
-        std::string err;
-        bool hard = false;
-        const JitKernels *jk = jit_lookup(d, cfg, allow_compile, &err, &hard);
-        if (jk && jk->encode_win) {
-            const long long blocks = (long long)stripes * (cfg.sub / (64 * cfg.W));
-            if (blocks > 0x7FFFFFFF) return fail(kInvalid, "batch too large");
-            const unsigned threads = 64u * (unsigned)((m + cfg.rows_per_wave - 1) / cfg.rows_per_wave);
-            long long in_stride = (long long)k * 8, out_stride = (long long)m * 8;
-            int n = stripes;
-            int bb = bytes;  // (windowed modules take the block size as an argument)
-            void *args[] = {(void *)&data_ptrs, &in_stride, (void *)&rec_ptrs, &out_stride, &n, &bb};
-            LH_HIP(hipModuleLaunchKernel(jk->encode_win, (unsigned)blocks, 1, 1, threads, 1, 1, 0, st, args, nullptr));
-            note_launch("lh_jit_encode_win(pointer table)");
-            return kOk;
-        }
-        if (hard) return fail(kHipError, err);
-    }
-    // Generic shapes (no specialised module, or one still compiling): the jump-table apply
-    // reads the data blocks and writes the recovery blocks through the tables themselves.
-    if (k > 1 && m > 1 && k + m <= 256 && bytes % 8 == 0 && bytes / 8 >= 4) {
-        const uint8_t *G = nullptr;
-        if (int rc = device_generator(d, k, m, &G, nullptr, st)) return rc;
-        JumpApplyArgs a{};
-        a.in_ptrs = data_ptrs;
-        a.in_n = k;
-        a.out_ptrs = rec_ptrs;
-        a.out_n = m;
-        a.coef = G;
-        a.coef_stride = 0;
-        a.n_in = k;
-        a.n_out = m;
-        a.bytes = bytes;
-        a.sub = bytes / 8;
-        a.stripes = stripes;
-        a.per_stripe = 0;
-        jump_layout(d, a, false);
-        LH_HIP(launch_apply_jump(a, st));
-        return kOk;
-    }
-    // Gather / strided encode / scatter, per chunk (m = 1, k = 1, sub < 4).  An invalid shape
-    // (m > 1 with k + m > 256 or bytes % 8 != 0) still gets recovery block 0 first, as the
-    // reference.
+    // kPathGather: gather / strided encode / scatter, per chunk (m = 1, k = 1, sub < 4).  An
+    // invalid shape (m > 1 with k + m > 256 or bytes % 8 != 0) still gets recovery block 0
+    // first, as the reference.
     const bool invalid = m > 1 && k > 1 && (k + m > 256 || bytes % 8 != 0);
     const long long per = (long long)(k + m) * bytes;
     uint8_t *buf = nullptr;
@@ -855,121 +898,29 @@ static int encode_batch_ptrs(int k, int m, int bytes, int stripes, uint8_t *cons
 
 static int decode_batch_ptrs(int k, int m, int bytes, int stripes, uint8_t *const *block_ptrs, uint8_t *d_rows,
                              int8_t *d_status, hipStream_t st, bool allow_compile = true) {
-    if (k < 1 || m < 1 || bytes <= 0 || stripes < 0 || k > 256 || m > 256)
-        return fail(kInvalid, "invalid k, m, block_bytes or stripes");
+    if (int rc = check_shape(k, m, bytes, stripes)) return rc;
     if (stripes == 0) return kOk;
     if (m > 1 && k > 1 && (k + m > 256 || bytes % 8 != 0))
         return fail(kInvalid, "k + m > 256 or block_bytes % 8 != 0");
     if (!block_ptrs || !d_rows) return fail(kInvalid, "null pointer table or rows");
     Device *d = nullptr;
     if (int rc = current_device(&d)) return rc;
-    JitConfig cfg;
-    if (k > 1 && m > 1 && jit_ptr_config_for(k, m, bytes, true, &cfg)) {
-        std::string err;
-        bool hard = false;
-        const JitKernels *jk = jit_lookup(d, cfg, allow_compile, &err, &hard);
-        if (hard) return fail(kHipError, err);
-        if (jk) {
-            if (jit_blocks(cfg, stripes) > 0x7FFFFFFF) return fail(kInvalid, "batch too large");
-            const uint8_t *zero = nullptr;
-            if (int rc = zero_page(d, (size_t)bytes, &zero, st)) return rc;
-            long long s1 = (long long)k * 8;
-            int n = stripes;
-            if (jk->decode_fused && std::getenv("LONGHAIR_AMD_NO_FUSED_PLAN") == nullptr) {
-                const uint8_t *gexp = d->gf_exp;
-                const int16_t *glog = d->gf_log;
-                void *args[] = {(void *)&block_ptrs, &s1, (void *)&d_rows, (void *)&d_status, (void *)&zero,
-                                (void *)&gexp, (void *)&glog, &n};
-                LH_HIP(hipModuleLaunchKernel(jk->decode_fused, (unsigned)jit_blocks(cfg, stripes), 1, 1, 256, 1, 1, 0,
-                                             st, args, nullptr));
-                note_launch("lh_jit_decode_fused(pointer table)");
-                return kOk;
-            }
-            const int e_max = k < m ? k : m;
-            const long long plan_stride = PlanView::bytes(k, m, e_max);
-            Workspace *w = nullptr;
-            if (int rc = run_planner(d, st, k, m, e_max, stripes, d_rows, d_status, 0, false, &w)) return rc;
-            long long s2 = plan_stride;
-            const uint8_t *plan = w->plan.ptr;
-            void *args[] = {(void *)&block_ptrs, &s1, (void *)&plan, &s2, (void *)&zero, &n};
-            LH_HIP(hipModuleLaunchKernel(jk->decode, (unsigned)jit_blocks(cfg, stripes), 1, 1, 256, 1, 1, 0, st, args,
-                                         nullptr));
-            note_launch("lh_jit_decode(pointer table)");
-            return kOk;
-        }
+    const Blocks slots = table_blocks(block_ptrs, k);
+    Route r;
+    if (int rc = route(d, true, k, m, bytes, slots, allow_compile, &r)) return rc;
+    if (r.path == kPathFused) return launch_jit_decode_fused(d, r, bytes, stripes, slots, d_rows, d_status, st);
+    if (r.path != kPathGather) {  // (k, m > 1) the planner, then the route's kernels through the table
+        const int e_max = k < m ? k : m;
+        const long long plan_stride = PlanView::bytes(k, m, e_max);
+        Workspace *w = nullptr;
+        if (int rc = run_planner(d, st, k, m, e_max, stripes, d_rows, d_status, 0, r.path == kPathJump, &w)) return rc;
+        if (r.path == kPathRegister) return launch_jit_decode(d, r, bytes, stripes, slots, w, plan_stride, st);
+        if (r.path == kPathWindowed)
+            return launch_jit_decode_wide(d, r, k, m, e_max, bytes, stripes, slots, w, plan_stride, st);
+        return launch_jump(d, k, m, bytes, stripes, slots, slots, w, st);
     }
-    // Large m: the planner, the windowed phase A reading the slots through the table (V_r
-    // back in place of R_r) and phase B through the same table.
-    if (k > 1 && m > 1 && !jit_config_for(k, m, bytes, true, &cfg) && jit_win_ptr_config_for(k, m, bytes, &cfg, true)) {
-        std::string err;
-        bool hard = false;
-        const JitKernels *wk = jit_lookup(d, cfg, allow_compile, &err, &hard);
-        if (hard) return fail(kHipError, err);
-        if (wk && wk->decode_wide) {
-            const int e_max = k < m ? k : m;
-            const long long plan_stride = PlanView::bytes(k, m, e_max);
-            const long long cps = cfg.sub / (64 * cfg.W);
-            if ((long long)stripes * cps > 0x7FFFFFFF) return fail(kInvalid, "batch too large");
-            Workspace *w = nullptr;
-            const uint8_t *zero = nullptr;
-            if (int rc = zero_page(d, (size_t)bytes, &zero, st)) return rc;
-            if (int rc = run_planner(d, st, k, m, e_max, stripes, d_rows, d_status, 0, false, &w)) return rc;
-            const unsigned threads = 64u * (unsigned)((m + cfg.rows_per_wave - 1) / cfg.rows_per_wave);
-            long long s1 = (long long)k * 8, s2 = plan_stride;
-            const uint8_t *plan = w->plan.ptr;
-            int n = stripes;
-            int bb = bytes;  // (windowed modules take the block size as an argument)
-            void *args[] = {(void *)&block_ptrs, &s1, (void *)&plan, &s2, (void *)&zero, &n, &bb};
-            LH_HIP(hipModuleLaunchKernel(wk->decode_wide, (unsigned)(stripes * cps), 1, 1, threads, 1, 1, 0, st, args,
-                                         nullptr));
-            note_launch("lh_jit_decode_wide(pointer table)");
-            InverseArgs ia{};
-            ia.ptrs = block_ptrs;
-            ia.plan = plan;
-            ia.plan_stride = plan_stride;
-            ia.k = k;
-            ia.m = m;
-            ia.e_max = e_max;
-            ia.bytes = bytes;
-            ia.stripes = stripes;
-            ia.order = (int *)(w->plan.ptr + plan_order_offset(stripes, plan_stride));
-            LH_HIP(launch_inverse(ia, st));
-            return kOk;
-        }
-    }
-    // Generic shapes: the planner, then the jump-table apply in place through the table (the
-    // strided decode's rules: dword lanes from sub = 4, and the overlapping last lane of a
-    // sub-block must share its neighbour's workgroup).
-    if (k > 1 && m > 1) {
-        const int sub = bytes / 8, jnch = (sub + 3) / 4;
-        if (sub >= 4 && !(sub % 4 != 0 && jnch > 1 && (jnch - 1) % 64 == 0)) {
-            const int e_max = k < m ? k : m;
-            const long long plan_stride = PlanView::bytes(k, m, e_max);
-            Workspace *w = nullptr;
-            if (int rc = run_planner(d, st, k, m, e_max, stripes, d_rows, d_status, 0, true, &w)) return rc;
-            JumpApplyArgs a{};
-            a.in_ptrs = block_ptrs;
-            a.out_ptrs = block_ptrs;
-            a.in_n = k;
-            a.out_n = k;
-            a.coef = w->plan.ptr + PlanView::w_offset(k, m, e_max);
-            a.coef_stride = plan_stride;
-            a.plan = w->plan.ptr;
-            a.plan_stride = plan_stride;
-            a.n_in = k;
-            a.n_out = e_max;
-            a.bytes = bytes;
-            a.sub = sub;
-            a.stripes = stripes;
-            a.per_stripe = 1;
-            a.order = (int *)(w->plan.ptr + plan_order_offset(stripes, plan_stride));
-            jump_layout(d, a, true);
-            LH_HIP(launch_apply_jump(a, st));
-            return kOk;
-        }
-    }
-    // Gather / strided decode / scatter, per chunk (m = 1, k = 1, tiny or lone-tail blocks).
-    // Only the slots the decode may have
+    // kPathGather: gather / strided decode / scatter, per chunk (m = 1, k = 1, tiny or lone-tail
+    // blocks).  Only the slots the decode may have
     // changed go back, judged by the rows before the call (a copy of the chunk's rows rides
     // at the end of the chunk): for k, m > 1 the slots that held recovery rows (row >= k) of
     // the stripes it decoded (status 0); for m = 1 the one output slot of cauchy_decode_m1
@@ -1240,8 +1191,9 @@ static int host_decode_batch(int k, int m, int bytes, int stripes, uint8_t *h_bl
 // device -- a one-stripe call from host memory cannot amortise a PCIe round trip (k29/m4:
 // ~35 us staged through the GPU against ~7 us on the host engine and ~9 us for the
 // reference).  kGpu: always on the device.  kHost: every all-host-memory call on the host
-// engine.  Device (or mixed) pointers always go to the device.  The library needs a GPU
-// under every policy.
+// engine.  Device (or mixed) pointers always go to the device.  Without a HIP device the
+// drop-in calls run on the host engine under kAuto and kHost (host_only below) and fail
+// with -2 under kGpu; batch calls always need a device.
 enum { kDispatchGpu = 0, kDispatchAuto = 1, kDispatchHost = 2 };
 
 static int env_dispatch() {
@@ -1572,29 +1524,18 @@ LH_API int cauchy_256_batch_prepare_stream(int k, int m, int block_bytes, int ma
         lh::Device *d = nullptr;
         if (int rc = lh::current_device(&d)) return rc;
         std::string err;
-        for (int dec = 0; dec < 2; ++dec) {
-            lh::JitConfig cfg;
-            if (lh::jit_config_for(k, m, block_bytes, dec == 1, &cfg) && !d->jit.get(cfg, &err))
-                return lh::fail(lh::kHipError, err);
-        }
-        {
-            lh::JitConfig cfg;
-            if (!lh::jit_config_for(k, m, block_bytes, false, &cfg) && lh::jit_win_config_for(k, m, block_bytes, &cfg) &&
-                !d->jit.get(cfg, &err))
-                return lh::fail(lh::kHipError, err);
-            if (!lh::jit_config_for(k, m, block_bytes, true, &cfg) && lh::jit_win_config_for(k, m, block_bytes, &cfg, true) &&
-                !d->jit.get(cfg, &err))
-                return lh::fail(lh::kHipError, err);
-        }
+        std::vector<lh::JitConfig> cfgs;
+        lh::shape_configs(k, m, block_bytes, false, lh::kFormStrided, &cfgs);
+        lh::shape_configs(k, m, block_bytes, true, lh::kFormStrided, &cfgs);
+        for (const lh::JitConfig &cfg : cfgs)
+            if (!d->jit.get(cfg, &err)) return lh::fail(lh::kHipError, err);
         if (max_stripes > 0 && k > 1 && m > 1) {
             const int e_max = k < m ? k : m;
             lh::JitConfig cfg;
             const bool generic = !lh::jit_config_for(k, m, block_bytes, true, &cfg);
             lh::Workspace *w = nullptr;
             hipStream_t st = (hipStream_t)stream;
-            if (int rc = lh::workspace(d, st,
-                                       lh::plan_order_offset(max_stripes, lh::PlanView::bytes(k, m, e_max)) +
-                                           (size_t)max_stripes * sizeof(int),
+            if (int rc = lh::workspace(d, st, lh::plan_workspace_bytes(k, m, e_max, max_stripes),
                                        generic ? (size_t)max_stripes * e_max * block_bytes : 0, &w))
                 return rc;
             const uint8_t *G = nullptr, *z = nullptr;
@@ -1610,13 +1551,11 @@ LH_API int cauchy_256_batch_prepare_ptrs(int k, int m, int block_bytes) {
         lh::Device *d = nullptr;
         if (int rc = lh::current_device(&d)) return rc;
         std::string err;
-        for (int dec = 0; dec < 2; ++dec) {
-            lh::JitConfig cfg;
-            const bool reg = lh::jit_config_for(k, m, block_bytes, dec == 1, &cfg);
-            if (reg ? lh::jit_ptr_config_for(k, m, block_bytes, dec == 1, &cfg)
-                    : lh::jit_win_ptr_config_for(k, m, block_bytes, &cfg, dec == 1))
-                if (!d->jit.get(cfg, &err)) return lh::fail(lh::kHipError, err);
-        }
+        std::vector<lh::JitConfig> cfgs;
+        lh::shape_configs(k, m, block_bytes, false, lh::kFormTable, &cfgs);
+        lh::shape_configs(k, m, block_bytes, true, lh::kFormTable, &cfgs);
+        for (const lh::JitConfig &cfg : cfgs)
+            if (!d->jit.get(cfg, &err)) return lh::fail(lh::kHipError, err);
         return 0;
     LH_CATCH
 }
@@ -1637,32 +1576,22 @@ LH_API int cauchy_256_jit_precompile(int k, int m, int block_bytes) {
     LH_TRY
         std::string err;
         std::vector<char> code;
-        lh::JitConfig cfg;
+        // the (k, m) block-size family modules too (one per (k, m) and role, shared by every block
+        // size) with LONGHAIR_AMD_PRECOMPILE_FAMILY=1, the pointer-table forms
+        // (cauchy_256_*_batch_ptrs) with LONGHAIR_AMD_PRECOMPILE_PTR=1
+        auto on = [](const char *name) {
+            const char *e = std::getenv(name);
+            return e && std::string(e) == "1";
+        };
+        const int forms = lh::kFormStrided | (on("LONGHAIR_AMD_PRECOMPILE_FAMILY") ? lh::kFormFamily : 0) |
+                          (on("LONGHAIR_AMD_PRECOMPILE_PTR") ? lh::kFormTable : 0);
         const char *part = std::getenv("LONGHAIR_AMD_PRECOMPILE_PART");
-        for (int dec = 0; dec < 2; ++dec) {
-            if (part && std::string(part) != (dec ? "dec" : "enc")) continue;
-            if (lh::jit_config_for(k, m, block_bytes, dec == 1, &cfg)) {
-                if (!lh::compile_code_object(cfg, &code, &err)) return lh::fail(lh::kHipError, err);
-                // the (k, m) block-size family modules too (one per (k, m) and role, shared by every
-                // block size), with LONGHAIR_AMD_PRECOMPILE_FAMILY=1
-                const char *fam = std::getenv("LONGHAIR_AMD_PRECOMPILE_FAMILY");
-                if (!cfg.family && fam && std::string(fam) == "1" &&
-                    lh::jit_family_config_for(k, m, block_bytes, &cfg, dec == 1) &&
-                    !lh::compile_code_object(cfg, &code, &err))
-                    return lh::fail(lh::kHipError, err);
-                // the pointer-table form (cauchy_256_*_batch_ptrs) as well, with LONGHAIR_AMD_PRECOMPILE_PTR=1
-                const char *ptr = std::getenv("LONGHAIR_AMD_PRECOMPILE_PTR");
-                if (ptr && std::string(ptr) == "1" && lh::jit_ptr_config_for(k, m, block_bytes, dec == 1, &cfg) &&
-                    !lh::compile_code_object(cfg, &code, &err))
-                    return lh::fail(lh::kHipError, err);
-            } else if (lh::jit_win_config_for(k, m, block_bytes, &cfg, dec == 1)) {
-                if (!lh::compile_code_object(cfg, &code, &err)) return lh::fail(lh::kHipError, err);
-                const char *ptr = std::getenv("LONGHAIR_AMD_PRECOMPILE_PTR");
-                if (ptr && std::string(ptr) == "1" && lh::jit_win_ptr_config_for(k, m, block_bytes, &cfg, dec == 1) &&
-                    !lh::compile_code_object(cfg, &code, &err))
-                    return lh::fail(lh::kHipError, err);
-            }
-        }
+        std::vector<lh::JitConfig> cfgs;
+        for (int dec = 0; dec < 2; ++dec)
+            if (!part || std::string(part) == (dec ? "dec" : "enc"))
+                lh::shape_configs(k, m, block_bytes, dec == 1, forms, &cfgs);
+        for (const lh::JitConfig &cfg : cfgs)
+            if (!lh::compile_code_object(cfg, &code, &err)) return lh::fail(lh::kHipError, err);
         return 0;
     LH_CATCH
 }
@@ -1684,16 +1613,13 @@ LH_API int cauchy_256_batch_path(int k, int m, int block_bytes, int what) {
             lh::jump_layout(d, a, what == 7);
             return a.dw;
         }
-        if (!lh::jit_config_for(k, m, block_bytes, what == 1, &cfg)) {
-            if (what == 0) return lh::jit_win_config_for(k, m, block_bytes, &cfg) ? 3 : 0;
-            return lh::jit_win_config_for(k, m, block_bytes, &cfg, true) ? 4 : 0;
-        }
+        std::vector<lh::JitConfig> cfgs;  // the strided module of the role: none, windowed or register network
+        lh::shape_configs(k, m, block_bytes, what == 1, lh::kFormStrided, &cfgs);
+        if (cfgs.empty()) return 0;
+        if (cfgs[0].win) return what == 0 ? 3 : 4;
         // Decode: 2 when the plan is computed inside the specialised kernel (jit_codec.hip,
-        // LH_FUSED: e_max <= 4, one stripe per <= 64 lanes, k <= 64).
-        const int e_max = k < m ? k : m;
-        if (what == 1 && e_max <= 4 && cfg.nch <= 64 && k <= 64 && std::getenv("LONGHAIR_AMD_NO_FUSED_PLAN") == nullptr)
-            return 2;
-        return 1;
+        // LH_FUSED; jit.cpp: cfg.plain = 0).
+        return what == 1 && !cfgs[0].plain ? 2 : 1;
     LH_CATCH
 }
 

@@ -5,7 +5,8 @@
 // itself is ~2 us of AVX-512 (profiles/r2_bench_k29m4.json, dropin_per_call).  The
 // dispatch policy (codec.cpp, cauchy_256_dispatch.h) sends such calls here by default
 // (AUTO: all-host calls with at most LONGHAIR_AMD_HOST_MAX_WORK bytes of XOR work) or when
-// the caller selects HOST; the library still requires a GPU.
+// the caller selects HOST.  In a process without a HIP device every drop-in call runs here
+// under AUTO and HOST (include/cauchy_256.h:15-18); only batch calls need a GPU.
 //
 // Both operations are one bit-sliced coefficient apply (same algebra as the GPU kernels):
 //   out[i] sub-row y  ^=  in[j] sub-block b   for every bit b of C[i][j] * 2^y,

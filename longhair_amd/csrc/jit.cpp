@@ -36,6 +36,22 @@ long long generator_ones(int k, int m) {
     return ones;
 }
 
+// LONGHAIR_AMD_PATH=generic: no specialised module for any shape.
+static bool forced_generic() {
+    const char *env = std::getenv("LONGHAIR_AMD_PATH");
+    return env && std::string(env) == "generic";
+}
+// LONGHAIR_AMD_JIT_DEFINES: extra -D style tuning knobs of every module (JitConfig::defines).
+static std::string jit_defines() {
+    const char *d = std::getenv("LONGHAIR_AMD_JIT_DEFINES");
+    return d ? d : "";
+}
+// The value of a tuning knob ("LH_CPS=" ...) in a configuration's defines, or dflt.
+static int knob(const std::string &defines, const char *name, int dflt) {
+    const size_t at = defines.find(name);
+    return at == std::string::npos ? dflt : std::atoi(defines.c_str() + at + std::strlen(name));
+}
+
 // The encode's block-size family serves (k, m, bytes) when: 16-byte-multiple blocks, 8-byte
 // lanes with at most 64 per stripe (bytes <= 4096), the 8 x m accumulator words of 8-byte
 // lanes within the register budget (m <= 6), at least two steps of columns (k >= 4), and, when
@@ -63,9 +79,7 @@ bool jit_config_for(int k, int m, int bytes, bool decode, JitConfig *cfg) {
 }
 
 static bool config_impl(int k, int m, int bytes, bool decode, JitConfig *cfg, bool allow_family) {
-    if (const char *env = std::getenv("LONGHAIR_AMD_PATH")) {
-        if (std::string(env) == "generic") return false;
-    }
+    if (forced_generic()) return false;
     if (k < 2 || m < 2 || k + m > 256 || bytes % 8 != 0 || bytes <= 0) return false;
     // k > 128 with few rows: the generic kernel.  Its straight-line network of > 128
     // columns took hiprtc ~7 minutes per module (k250/m3) for a shape outside the
@@ -131,38 +145,31 @@ static bool config_impl(int k, int m, int bytes, bool decode, JitConfig *cfg, bo
     // as m = 3 does), of which a call uses one.
     cfg->role = decode ? 2 : 1;
     cfg->plain = decode && !(emax <= 4 && nch2 <= 64 && k <= 64 && std::getenv("LONGHAIR_AMD_NO_FUSED_PLAN") == nullptr);
-    cfg->defines.clear();
-    if (const char *d = std::getenv("LONGHAIR_AMD_JIT_DEFINES")) cfg->defines = d;
+    cfg->defines = jit_defines();
     // The LDS encode of strided batches fetches LH_CPS = 5 columns per DMA step (one step in
     // flight) and runs one 4-wave workgroup per CU (dynamic LDS pads the rest): k29/m4 encode
     // 0.502-0.509 -> 0.489-0.491 ms against the one-column ring at two workgroups per CU
     // (profiles/r9e_tune_k29m4_cps.txt; 3 columns 0.496, 4: 0.501, 6: 0.498, 7: 0.513; two
     // workgroups per CU 0.534; jit_codec.hip LH_CPS).  At least two steps (k >= 4).
     // Tuning overrides in LONGHAIR_AMD_JIT_DEFINES: LH_CPS=, LH_WGCU=, LH_WPB=.
-    auto knob = [&](const char *name, int dflt) {
-        const size_t at = cfg->defines.find(name);
-        return at == std::string::npos ? dflt : std::atoi(cfg->defines.c_str() + at + std::strlen(name));
-    };
     // A decode module always streams one column per step (cps = 1).
     cfg->cps = 1;
     if (!decode && cfg->lds) cfg->cps = std::max(1, std::min(5, k / 2));
-    cfg->cps = knob("LH_CPS=", cfg->cps);
+    cfg->cps = knob(cfg->defines, "LH_CPS=", cfg->cps);
     if (cfg->cps > 1 && !(!decode && cfg->lds && k >= 2 * cfg->cps)) cfg->cps = 1;
-    cfg->wgcu = knob("LH_WGCU=", cfg->cps > 1 ? 1 : 0);
-    const int wpb = knob("LH_WPB=", 4);
+    cfg->wgcu = knob(cfg->defines, "LH_WGCU=", cfg->cps > 1 ? 1 : 0);
+    const int wpb = knob(cfg->defines, "LH_WPB=", 4);
     cfg->enc_wpb = (cfg->cps > 1 && wpb >= 1 && wpb <= 8) ? wpb : 4;
     // Block-size family (jit_codec.hip LH_FAMILY): the multi-column-step encode with the block
     // size a kernel argument, keyed by (k, m) alone.
     cfg->family = 0;
     // (LH_FAMILY=1, tests: the family module even where a size-specialised one would serve)
-    if (allow_family && knob("LH_FAMILY=", 0) && jit_family_config_for(k, m, bytes, cfg, decode)) return true;
+    if (allow_family && knob(cfg->defines, "LH_FAMILY=", 0)) (void)jit_family_config_for(k, m, bytes, cfg, decode);
     return true;
 }
 
 bool jit_family_config_for(int k, int m, int bytes, JitConfig *cfg, bool decode) {
-    if (const char *env = std::getenv("LONGHAIR_AMD_PATH")) {
-        if (std::string(env) == "generic") return false;
-    }
+    if (forced_generic()) return false;
     if (!jit_family_ok(k, m, bytes, decode)) return false;
     if (decode && std::getenv("LONGHAIR_AMD_NO_FUSED_PLAN") != nullptr) return false;
     JitConfig c;
@@ -178,15 +185,13 @@ bool jit_family_config_for(int k, int m, int bytes, JitConfig *cfg, bool decode)
     c.role = decode ? 2 : 1;
     c.plain = 0;
     c.family = 1;
-    if (const char *d = std::getenv("LONGHAIR_AMD_JIT_DEFINES")) c.defines = d;
-    auto knob = [&](const char *name, int dflt) {
-        const size_t at = c.defines.find(name);
-        return at == std::string::npos ? dflt : std::atoi(c.defines.c_str() + at + std::strlen(name));
-    };
+    c.defines = jit_defines();
     c.cps = std::max(2, std::min(5, k / 2));
     // (tuning knobs that switch off what the family kernel is made of leave it out)
-    if (knob("LH_LDS=", 1) == 0 || knob("LH_CPS=", c.cps) < 2 || knob("LH_WPB=", 4) != 4) return false;
-    c.wgcu = knob("LH_WGCU=", decode ? 0 : 1);  // (the decode: two workgroups per CU, as its size-specialised form)
+    if (knob(c.defines, "LH_LDS=", 1) == 0 || knob(c.defines, "LH_CPS=", c.cps) < 2 || knob(c.defines, "LH_WPB=", 4) != 4)
+        return false;
+    // (the decode: two workgroups per CU, as its size-specialised form)
+    c.wgcu = knob(c.defines, "LH_WGCU=", decode ? 0 : 1);
     c.enc_wpb = 4;
     *cfg = c;
     return true;
@@ -215,9 +220,7 @@ bool jit_win_ptr_config_for(int k, int m, int bytes, JitConfig *cfg, bool decode
 }
 
 bool jit_win_config_for(int k, int m, int bytes, JitConfig *cfg, bool decode) {
-    if (const char *env = std::getenv("LONGHAIR_AMD_PATH")) {
-        if (std::string(env) == "generic") return false;
-    }
+    if (forced_generic()) return false;
     if (k < 2 || m < 2 || k + m > 256 || bytes % 8 != 0 || bytes <= 0) return false;
     const int sub = bytes / 8, W = 4;
     if (sub % (64 * W) != 0) return false;
@@ -251,8 +254,7 @@ bool jit_win_config_for(int k, int m, int bytes, JitConfig *cfg, bool decode) {
     cfg->win_lds = 1;
     if ((m + cfg->rows_per_wave - 1) / cfg->rows_per_wave > 16) return false;  // <= 1024 threads
     if (decode && m > 64) return false;  // the plan's used-row mask is one 64-lane ballot
-    cfg->defines.clear();
-    if (const char *d = std::getenv("LONGHAIR_AMD_JIT_DEFINES")) cfg->defines = d;
+    cfg->defines = jit_defines();
     return true;
 }
 

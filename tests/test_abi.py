@@ -84,6 +84,38 @@ def test_specialisation_policy():
     assert longhair_amd.batch_path(128, 32, 1000) == "generic"
 
 
+# (k, m, bytes, what, code): cauchy_256_batch_path on both sides of each boundary of the batch
+# routes, recorded from the library before codec.cpp's routes were collapsed into one function
+# (what 0 / 1: encode / decode path, 2 / 5: LDS staging, 8 / 9: block-size family).
+CLASSIFICATION = [
+    (29, 4, 1296, 0, 1), (29, 4, 1296, 1, 2), (29, 8, 1296, 1, 1),
+    (64, 4, 1296, 1, 2), (65, 4, 1296, 1, 1),          # fused plan: k <= 64
+    (8, 4, 4096, 1, 2), (8, 3, 8128, 1, 1),            # ... one stripe per <= 64 lanes
+    (4, 8, 64, 1, 2), (5, 8, 64, 1, 1), (10, 4, 64, 1, 2), (10, 5, 64, 1, 1),  # ... e_max <= 4
+    (9, 8, 64, 1, 1), (9, 9, 64, 1, 0),                # specialised decode: e_max * m <= 64
+    (40, 12, 2048, 0, 1), (40, 13, 2048, 0, 3),        # register network: m <= 12, else windowed
+    (10, 12, 64, 0, 1), (10, 13, 64, 0, 0),            # ... or generic (sub % 256 != 0)
+    (20, 64, 2048, 1, 4), (20, 65, 2048, 1, 0), (20, 65, 2048, 0, 3),  # windowed decode: m <= 64
+    (40, 20, 4096, 1, 4), (40, 20, 4104, 1, 0), (40, 20, 4096, 0, 3), (40, 20, 4104, 0, 0),
+    (128, 4, 1296, 0, 1), (129, 4, 1296, 0, 0),        # register network: k <= 128
+    (128, 32, 8192, 0, 3), (128, 32, 8192, 1, 4),
+    (200, 56, 2048, 0, 3), (200, 57, 2048, 0, 0),      # k + m <= 256
+    (29, 4, 1300, 0, 0),                               # bytes % 8
+    (29, 4, 1296, 2, 1), (29, 4, 1304, 2, 0), (29, 4, 1040, 2, 0), (29, 8, 1296, 2, 0),
+    (64, 4, 64, 2, 0), (64, 4, 4096, 5, 1),
+    (29, 4, 1296, 8, 1), (29, 4, 1304, 8, 0), (29, 4, 4096, 8, 1), (29, 4, 4112, 8, 0),
+    (29, 6, 1296, 8, 1), (29, 7, 1296, 8, 0), (3, 4, 1296, 8, 0),
+    (29, 4, 1296, 9, 1), (29, 5, 1296, 9, 0), (29, 4, 192, 9, 0), (64, 4, 1296, 9, 1), (65, 4, 1296, 9, 0),
+]
+
+
+def test_classification_table():
+    import longhair_amd
+    path = longhair_amd.lib().cauchy_256_batch_path
+    got = [(k, m, b, what, path(k, m, b, what)) for k, m, b, what, _ in CLASSIFICATION]
+    assert got == CLASSIFICATION
+
+
 def test_lds_staging_policy():
     """jit.cpp jit_config_for: the register networks stage their columns by LDS-DMA for 8-byte
     lanes, whole stripes per wave and 16-byte-multiple blocks, unless a stripe's partial last
