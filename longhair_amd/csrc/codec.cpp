@@ -610,8 +610,7 @@ static int launch_jit_decode_wide(Device *d, const Route &r, int k, int m, int e
 // of a slot before its overwrite (lone_tail).
 static void jump_layout(const Device *d, JumpApplyArgs &a, bool in_place) {
     bool two = a.n_out <= 4 && a.sub >= 8 && (!in_place || (a.sub >= 512 && !lone_tail(a.sub, 8)));
-    const char *fb = std::getenv("LONGHAIR_AMD_INV_FALLBACK");  // (tests: the in-asm table)
-    if (fb && std::atoi(fb)) two = false;
+    if (inv_fallback_forced()) two = false;  // (tests: the in-asm table)
     a.dw = two && d->jump2 ? 2 : 1;
     a.nch = (a.sub + 4 * a.dw - 1) / (4 * a.dw);
     a.wps = (a.nch + 63) / 64;

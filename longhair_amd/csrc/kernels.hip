@@ -33,6 +33,7 @@
 #include <cstdlib>
 #include <map>
 #include <mutex>
+#include <string>
 
 #include "kernels.hpp"
 
@@ -664,6 +665,72 @@ __global__ void __launch_bounds__(256) lh_frame_kernel(lh::FrameArgs a) {
 // the same bodies inside the asm statement (its fallback, lh_inverse_dma_body).
 #include "inv_jump.inc"
 
+// The absolute address of a jump table, from a PC-relative relocation.
+#define LH_TABLE_ADDR(sym, lo, hi)                            \
+    asm volatile("s_getpc_b64 s[92:93]\n"                     \
+                 "s_add_u32 s92, s92, " #sym "@rel32@lo+4\n"   \
+                 "s_addc_u32 s93, s93, " #sym "@rel32@hi+12\n" \
+                 "s_mov_b32 %0, s92\n"                        \
+                 "s_mov_b32 %1, s93\n"                        \
+                 : "=s"(lo), "=s"(hi)                         \
+                 :                                            \
+                 : "s92", "s93", "scc")
+
+constexpr uint32_t kJumpBodies = 256;  // bodies per table
+// What differs between the jump table of one-dword lanes (lh_inv_gtab: phase B and
+// lh_apply_jump_kernel) and of two-dword lanes (lh_inv_gtab2: lh_apply_jump2_kernel).  (The
+// table's symbol is asm text: the kernels hand it to LH_TABLE_ADDR themselves.)
+template <int DW>
+struct lh_jt;
+template <>
+struct lh_jt<1> {
+    typedef uint32_t lane;                      // a lane's 4 * DW bytes of one sub-block
+    static constexpr int kOuts = 8;             // outputs per wave: accumulators acc[8][8]
+    static constexpr uint32_t kBody = 68;       // bytes per body: 8 v_bitop3_b32 + s_setpc_b64
+    // A table whose address has a low word above kMaxLo straddles a 4 GiB boundary: its body
+    // addresses do not share one high word, so it is not entered (never seen).
+    static constexpr uint32_t kMaxLo = 0xFFFFFFFFu - kJumpBodies * kBody;
+    static constexpr int kThreads = 1024;       // launch bounds (124 VGPRs)
+    static constexpr bool kAsmFallback = true;  // lh_mul_jump_idx8 serves an unusable table
+};
+template <>
+struct lh_jt<2> {
+    typedef uint32_t lane __attribute__((ext_vector_type(2)));
+    static constexpr int kOuts = 4;  // acc[4][16]
+    static constexpr uint32_t kBody = 132;
+    static constexpr uint32_t kMaxLo = 0xFFFFFFFFu - kJumpBodies * kBody;
+    static constexpr int kThreads = 768;  // ~150 VGPRs: 3 waves per SIMD
+    static constexpr bool kAsmFallback = false;
+};
+
+// The 16-entry XOR tables of a lane's sub-blocks 0..3 (tl) and 4..7 (th): entry q is the XOR
+// of the sub-blocks in the bits of q.
+template <class L>
+__device__ __forceinline__ void lh_nibble_tables(const L (&d)[8], L (&tl)[16], L (&th)[16]) {
+    tl[0] = th[0] = L{};
+#pragma unroll
+    for (int q = 1; q < 16; ++q) {
+        const int low = __builtin_ctz(q), pre = q & (q - 1);
+        tl[q] = pre ? (tl[pre] ^ d[low]) : d[low];
+        th[q] = pre ? (th[pre] ^ d[4 + low]) : d[4 + low];
+    }
+}
+
+// f(std::integral_constant<int, n>) for a wave-uniform n in 0..MAX (MAX <= 8), so the row and
+// column loops are instantiated per output count and no slot jumps for an unused output.
+template <int MAX, class F>
+__device__ __forceinline__ void lh_for_count(int n, F &&f) {
+    switch (n) {  // wave-uniform
+#define LH_COUNT_CASE(c) \
+    case c:              \
+        if constexpr (c < MAX) { f(std::integral_constant<int, c>{}); break; }
+        LH_COUNT_CASE(0) LH_COUNT_CASE(1) LH_COUNT_CASE(2) LH_COUNT_CASE(3) LH_COUNT_CASE(4) LH_COUNT_CASE(5)
+        LH_COUNT_CASE(6) LH_COUNT_CASE(7)  // (c >= MAX falls through to the default)
+#undef LH_COUNT_CASE
+        default: f(std::integral_constant<int, MAX>{}); break;
+    }
+}
+
 // The in-asm table: the 8 outputs of a wave keep their accumulators in pinned registers
 // v[40 + 8i .. 40 + 8i + 7]; one asm statement per row builds the 8 jump targets from the
 // packed coefficient bytes (masked to 8 bits in the asm), enters the table once per output
@@ -785,13 +852,7 @@ struct lh_pb_ctx {
         uint32_t v[8];
 #pragma unroll
         for (int y = 0; y < 8; ++y) v[y] = buf[(j * 8 + y) * 64 + lane];
-        tl[0] = th[0] = 0;
-#pragma unroll
-        for (int q = 1; q < 16; ++q) {
-            const int low = __builtin_ctz(q), pre = q & (q - 1);
-            tl[q] = pre ? (tl[pre] ^ v[low]) : v[low];
-            th[q] = pre ? (th[pre] ^ v[4 + low]) : v[4 + low];
-        }
+        lh_nibble_tables(v, tl, th);
     }
     __device__ __forceinline__ void store(int ch, int out, const uint32_t (&acc)[8]) const {
         uint8_t *dst = (ptab ? lane_ptr(op, out) : sbase + (long long)pv.out_slot(out) * a.bytes) + ch * 256 + lane * 4;
@@ -876,6 +937,30 @@ __device__ __forceinline__ void lh_inverse_dma_body(const lh::InverseArgs &a, ui
 // outputs (nout == 0) never executes the statement.
 __global__ void lh_inv_gtab_holder() { asm volatile(LH_INV_GTAB_TEXT); }
 
+// The statement of N outputs for row (or column) r: lane r of t[i] holds output i's body address.
+#define LH_GT_CASE(n)                                                                                       \
+    if constexpr (N == n)                                                                                   \
+        asm volatile(LH_INV_JUMPG##n##_ASM : LH_INV_JUMPG##n##_OUTS(acc) : LH_INV_JUMPG_INS(tl, th, t),      \
+                     [r] "s"(r), [hi] "s"(hi) : "s92", "s93", "s94", "s95", "s97", "scc");
+#define LH_GT2_CASE(n)                                                                                       \
+    if constexpr (N == n)                                                                                    \
+        asm volatile(LH_INV_JUMPG2_##n##_ASM : LH_INV_JUMPG2_##n##_OUTS(acc) : LH_INV_JUMPG2_INS(tl, th, t),  \
+                     [r] "s"(r), [hi] "s"(hi) : "s92", "s93", "s94", "s95", "s97", "scc");
+template <int N>
+__device__ __forceinline__ void lh_jump_stmt(uint32_t (&acc)[8][8], const uint32_t (&tl)[16], const uint32_t (&th)[16],
+                                             const uint32_t (&t)[8], int r, uint32_t hi) {
+    LH_GT_CASE(1) LH_GT_CASE(2) LH_GT_CASE(3) LH_GT_CASE(4) LH_GT_CASE(5) LH_GT_CASE(6) LH_GT_CASE(7)
+    LH_GT_CASE(8)
+}
+template <int N>
+__device__ __forceinline__ void lh_jump_stmt(uint32_t (&acc)[4][16], const lh_jt<2>::lane (&tl)[16],
+                                             const lh_jt<2>::lane (&th)[16], const uint32_t (&t)[4], int r,
+                                             uint32_t hi) {
+    LH_GT2_CASE(1) LH_GT2_CASE(2) LH_GT2_CASE(3) LH_GT2_CASE(4)
+}
+#undef LH_GT_CASE
+#undef LH_GT2_CASE
+
 #ifndef LH_GT_CHECK
 // Debug build (make -C longhair_amd/csrc LH_DEBUG=1): every jump target is checked to be a
 // body of the table before the call, and GPR indexing off after it; a failed check skips
@@ -883,26 +968,21 @@ __global__ void lh_inv_gtab_holder() { asm volatile(LH_INV_GTAB_TEXT); }
 #define LH_GT_CHECK 0
 #endif
 
-template <int N>
-__device__ __forceinline__ bool lh_mul_jump_g(uint32_t (&acc)[8][8], const uint32_t (&tl)[16],
-                                              const uint32_t (&th)[16], const uint32_t (&t)[8], int r,
-                                              uint32_t tlo, uint32_t hi) {
+template <int N, int DW>
+__device__ __forceinline__ bool lh_mul_jump_g(uint32_t (&acc)[lh_jt<DW>::kOuts][8 * DW],
+                                              const typename lh_jt<DW>::lane (&tl)[16],
+                                              const typename lh_jt<DW>::lane (&th)[16],
+                                              const uint32_t (&t)[lh_jt<DW>::kOuts], int r, uint32_t tlo, uint32_t hi) {
 #if LH_GT_CHECK
 #pragma unroll
     for (int i = 0; i < N; ++i) {
         const uint32_t d = (uint32_t)__builtin_amdgcn_readlane((int)t[i], r) - tlo;
-        if (d >= 256u * 68u || d % 68u != 0u) return false;  // wave-uniform
+        if (d >= kJumpBodies * lh_jt<DW>::kBody || d % lh_jt<DW>::kBody != 0u) return false;  // wave-uniform
     }
 #else
     (void)tlo;
 #endif
-#define LH_GT_CASE(n)                                                                                       \
-    if constexpr (N == n)                                                                                   \
-        asm volatile(LH_INV_JUMPG##n##_ASM : LH_INV_JUMPG##n##_OUTS(acc) : LH_INV_JUMPG_INS(tl, th, t),      \
-                     [r] "s"(r), [hi] "s"(hi) : "s92", "s93", "s94", "s95", "s97", "scc");
-    LH_GT_CASE(1) LH_GT_CASE(2) LH_GT_CASE(3) LH_GT_CASE(4) LH_GT_CASE(5) LH_GT_CASE(6) LH_GT_CASE(7)
-    LH_GT_CASE(8)
-#undef LH_GT_CASE
+    lh_jump_stmt<N>(acc, tl, th, t, r, hi);
 #if LH_GT_CHECK
     // MODE.GPR_IDX_EN (bit 27 of HW_REG_MODE on gfx9): must be off again after the statement.
     if (__builtin_amdgcn_s_getreg(1 | (27 << 6) | (0 << 11)) != 0) return false;
@@ -930,10 +1010,10 @@ __device__ __forceinline__ void lh_inverse_gt_body(const lh::InverseArgs &a, uin
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const uint32_t c = (C.rslot != 0xFFu && i < nout) ? cf[out_of(i) * C.m + C.lane] : 0u;
-            t[i] = tlo + c * 68u;
+            t[i] = tlo + c * lh_jt<1>::kBody;
         }
     }
-    auto run = [&](auto no) {
+    lh_for_count<8>(nout, [&](auto no) {
         constexpr int N = decltype(no)::value;
         uint32_t acc[8][8];
 #pragma unroll
@@ -946,7 +1026,7 @@ __device__ __forceinline__ void lh_inverse_gt_body(const lh::InverseArgs &a, uin
                 for (int j = 0; rest && j < 8; ++j, rest &= rest - 1) {
                     uint32_t tl[16], th[16];
                     C.tables(buf, j, tl, th);
-                    if (ok) ok = lh_mul_jump_g<N>(acc, tl, th, t, __builtin_ctzll(rest), tlo, thi);
+                    if (ok) ok = lh_mul_jump_g<N, 1>(acc, tl, th, t, __builtin_ctzll(rest), tlo, thi);
                 }
             }
         }, [&](int ch) {
@@ -960,37 +1040,16 @@ __device__ __forceinline__ void lh_inverse_gt_body(const lh::InverseArgs &a, uin
                 for (int y = 0; y < 8; ++y) acc[i][y] = 0;
             }
         });
-    };
-    switch (nout) {  // wave-uniform
-        case 0: run(std::integral_constant<int, 0>{}); break;
-        case 1: run(std::integral_constant<int, 1>{}); break;
-        case 2: run(std::integral_constant<int, 2>{}); break;
-        case 3: run(std::integral_constant<int, 3>{}); break;
-        case 4: run(std::integral_constant<int, 4>{}); break;
-        case 5: run(std::integral_constant<int, 5>{}); break;
-        case 6: run(std::integral_constant<int, 6>{}); break;
-        case 7: run(std::integral_constant<int, 7>{}); break;
-        default: run(std::integral_constant<int, 8>{}); break;
-    }
+    });
 }
 
-// The table's address comes from a PC-relative relocation.  A table that would straddle a
-// 4 GiB boundary (the body addresses' high word differs; never seen) or a.jump_fallback
-// (tests) takes the in-asm table instead.
-__global__ void __launch_bounds__(1024) lh_inverse_gt_kernel(lh::InverseArgs a) {
+// An unusable table or a.jump_fallback (tests) takes the in-asm table instead.
+__global__ void __launch_bounds__(lh_jt<1>::kThreads) lh_inverse_gt_kernel(lh::InverseArgs a) {
     __shared__ __attribute__((aligned(16))) uint32_t lvA[8 * 8 * 64];
     __shared__ __attribute__((aligned(16))) uint32_t lvB[8 * 8 * 64];
     uint32_t tlo, thi;
-    asm volatile(
-        "s_getpc_b64 s[92:93]\n"
-        "s_add_u32 s92, s92, lh_inv_gtab@rel32@lo+4\n"
-        "s_addc_u32 s93, s93, lh_inv_gtab@rel32@hi+12\n"
-        "s_mov_b32 %0, s92\n"
-        "s_mov_b32 %1, s93\n"
-        : "=s"(tlo), "=s"(thi)
-        :
-        : "s92", "s93", "scc");
-    if (a.jump_fallback || tlo > 0xFFFFFFFFu - 256u * 68u) {
+    LH_TABLE_ADDR(lh_inv_gtab, tlo, thi);
+    if (a.jump_fallback || tlo > lh_jt<1>::kMaxLo) {
         lh_inverse_dma_body(a, lvA, lvB);
         return;
     }
@@ -1031,9 +1090,12 @@ __global__ void __launch_bounds__(1024) lh_order_kernel(const uint8_t *__restric
 // body address of output i for column j held in lane j of t[i].  Column loads are unaligned
 // dword loads (a sub-block starts 2-byte aligned at 1296-byte blocks); the next column is in
 // flight while the current one is combined.
+//
+// The family is written once over the lane width DW (lh_jt<DW>): lh_apply_jump_kernel has
+// one-dword lanes and 8 outputs per wave; lh_apply_jump2_kernel (a.dw == 2) two-dword lanes, so
+// half the jumps per byte, at twice the table registers and 4 outputs per wave (at most 12
+// waves per workgroup).
 namespace {
-typedef uint32_t lh_u32u __attribute__((aligned(1)));
-
 struct lh_ja_lane {
     long long stripe;   // (clamped to a valid stripe for the loads of an inactive lane)
     int p;              // the lane's byte offset in every sub-block
@@ -1042,12 +1104,13 @@ struct lh_ja_lane {
 
 // (an inactive lane -- past the last stripe, or past the chunk's sub-block bytes -- loads
 // nothing: exec-masked, no memory request)
-__device__ __forceinline__ void lh_ja_load(uint32_t (&d)[8], const uint8_t *col, int sub, bool active) {
+template <class L>
+__device__ __forceinline__ void lh_ja_load(L (&d)[8], const uint8_t *col, int sub, bool active) {
 #pragma unroll
-    for (int b = 0; b < 8; ++b) d[b] = 0;
+    for (int b = 0; b < 8; ++b) d[b] = L{};
     if (active) {
 #pragma unroll
-        for (int b = 0; b < 8; ++b) d[b] = *(const lh_u32u *)(col + (long long)b * sub);
+        for (int b = 0; b < 8; ++b) __builtin_memcpy(&d[b], col + (long long)b * sub, sizeof(L));  // unaligned
     }
 }
 
@@ -1065,59 +1128,58 @@ __device__ __forceinline__ uint8_t *lh_ja_out(const lh::JumpApplyArgs &a, const 
     return a.out + l.stripe * a.out_stride + (long long)o * a.bytes + l.p;
 }
 
-__device__ __forceinline__ void lh_ja_tables(const uint32_t (&d)[8], uint32_t (&tl)[16], uint32_t (&th)[16]) {
-    tl[0] = th[0] = 0;
-#pragma unroll
-    for (int q = 1; q < 16; ++q) {
-        const int low = __builtin_ctz(q), pre = q & (q - 1);
-        tl[q] = pre ? (tl[pre] ^ d[low]) : d[low];
-        th[q] = pre ? (th[pre] ^ d[4 + low]) : d[4 + low];
-    }
-}
-
 // One round: outputs i0 .. i0 + N - 1 of this wave over every input column.  GT: the table
-// once per code object (lh_mul_jump_g); else the in-asm table (lh_mul_jump_idx8, a table
-// straddling a 4 GiB boundary; coefficient 0 = body 0 leaves unused outputs unchanged).
-template <int N, bool GT, bool PTR = false>
-__device__ __forceinline__ void lh_ja_round(const lh::JumpApplyArgs &a, const lh_ja_lane &l, const uint8_t *coef,
-                                            int i0, uint32_t (&acc)[8][8], uint32_t tlo, uint32_t thi) {
+// once per code object (lh_mul_jump_g); else the in-asm table (lh_mul_jump_idx8, DW 1 only;
+// coefficient 0 = body 0 leaves unused outputs unchanged).  false: a failed debug check.
+template <int N, int DW, bool GT, bool PTR>
+__device__ __forceinline__ bool lh_ja_round(const lh::JumpApplyArgs &a, const lh_ja_lane &l, const uint8_t *coef,
+                                            int i0, uint32_t (&acc)[lh_jt<DW>::kOuts][8 * DW], uint32_t tlo,
+                                            uint32_t thi) {
+    using J = lh_jt<DW>;
+    static_assert(GT || J::kAsmFallback, "no in-asm table at this lane width");
     const int lane = threadIdx.x & 63;
+    bool ok = true;
     for (int jq = 0; jq * 64 < a.n_in; ++jq) {  // 64 columns per block of body addresses
         const int jc = jq * 64 + lane;
-        uint32_t t[8], cpk0 = 0, cpk1 = 0;
+        uint32_t t[J::kOuts], cpk[2] = {0, 0};
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
+        for (int i = 0; i < J::kOuts; ++i) {
             const uint32_t c = (i < N && jc < a.n_in) ? coef[(long long)(i0 + i) * a.n_in + jc] : 0u;
-            t[i] = tlo + c * 68u;
-            if (i < 4) cpk0 |= c << (8 * i);
-            else cpk1 |= c << (8 * (i - 4));
+            t[i] = tlo + c * J::kBody;
+            cpk[i >> 2 & 1] |= c << (8 * (i & 3));
         }
         const int nj = a.n_in - jq * 64 < 64 ? a.n_in - jq * 64 : 64;
-        uint32_t cur[8];
+        typename J::lane cur[8];
         lh_ja_load(cur, lh_ja_col<PTR>(a, l, jq * 64), a.sub, l.active);
         for (int jl = 0; jl < nj; ++jl) {  // wave-uniform
             const int jn = jq * 64 + jl + 1 < a.n_in ? jq * 64 + jl + 1 : jq * 64 + jl;  // (the last reloads itself)
-            uint32_t nxt[8];
+            typename J::lane nxt[8], tl[16], th[16];
             lh_ja_load(nxt, lh_ja_col<PTR>(a, l, jn), a.sub, l.active);
-            uint32_t tl[16], th[16];
-            lh_ja_tables(cur, tl, th);
+            lh_nibble_tables(cur, tl, th);
             if constexpr (GT) {
-                (void)lh_mul_jump_g<N>(acc, tl, th, t, jl, tlo, thi);
+                if (ok) ok = lh_mul_jump_g<N, DW>(acc, tl, th, t, jl, tlo, thi);
             } else {
-                lh_mul_jump_idx8((uint32_t)__builtin_amdgcn_readlane((int)cpk0, jl),
-                                 (uint32_t)__builtin_amdgcn_readlane((int)cpk1, jl), acc, tl, th);
+                lh_mul_jump_idx8((uint32_t)__builtin_amdgcn_readlane((int)cpk[0], jl),
+                                 (uint32_t)__builtin_amdgcn_readlane((int)cpk[1], jl), acc, tl, th);
             }
 #pragma unroll
             for (int b = 0; b < 8; ++b) cur[b] = nxt[b];
         }
     }
+    return ok;
 }
 
-template <bool GT, bool PTR>
-__device__ __forceinline__ void lh_apply_jump_body(const lh::JumpApplyArgs &a, uint32_t tlo, uint32_t thi) {
-    const int lane = threadIdx.x & 63;
+// usable: the table may be entered.  A failed check (here, or in the debug build's target
+// check) poisons the outputs, so the parity tests fail loudly.
+template <int DW, bool GT, bool PTR>
+__device__ __forceinline__ void lh_apply_jump_body(const lh::JumpApplyArgs &a, bool usable, uint32_t tlo,
+                                                   uint32_t thi) {
+    constexpr int NO = lh_jt<DW>::kOuts;
     const int g = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), ng = (int)(blockDim.x >> 6);
+    // The lane's place: one stripe's 64-lane chunk per workgroup (per_stripe, the stripes in
+    // a.order when given) or flat over (stripe, chunk).
     lh_ja_lane l;
+    const int lane = threadIdx.x & 63;
     int c;
     if (a.per_stripe) {
         l.stripe = blockIdx.x / a.wps;
@@ -1133,226 +1195,50 @@ __device__ __forceinline__ void lh_apply_jump_body(const lh::JumpApplyArgs &a, u
         l.active = l.stripe < a.stripes;
         if (!l.active) l.stripe = a.stripes - 1;
     }
-    // The last chunk of a sub-block re-reads its final 4 bytes (overlapping its neighbour
+    // The last chunk of a sub-block re-reads its final 4 * DW bytes (overlapping its neighbour
     // with identical results) instead of running past the sub-block.
-    l.p = c == a.nch - 1 ? a.sub - 4 : 4 * c;
+    l.p = c == a.nch - 1 ? a.sub - 4 * DW : 4 * DW * c;
     const uint8_t *pl = a.plan ? a.plan + l.stripe * a.plan_stride : nullptr;
     const int n_out = pl ? pl[0] : a.n_out;  // per_stripe: workgroup-uniform
     if (pl && n_out == 0) return;           // workgroup-uniform: nothing erased
     const uint8_t *coef = a.coef + l.stripe * a.coef_stride;
-    const int rounds = (a.n_out + 8 * ng - 1) / (8 * ng);  // the same for every wave (barriers)
+    const int rounds = (a.n_out + NO * ng - 1) / (NO * ng);  // the same for every wave (barriers)
     for (int q = 0; q < rounds; ++q) {
-        const int i0 = 8 * (q * ng + g);
+        const int i0 = NO * (q * ng + g);
         int nout = n_out - i0;
-        nout = nout < 0 ? 0 : (nout > 8 ? 8 : nout);  // wave-uniform
+        nout = nout < 0 ? 0 : (nout > NO ? NO : nout);  // wave-uniform
         // In place (a single round): a wave past its stripe's e neither reads nor writes, and
         // an ended wave no longer counts at the workgroup barrier, so it leaves now and frees
         // its slot (random e: k200/m56 keeps ~half of each workgroup's waves).
         if (pl && nout == 0) return;
-        uint32_t acc[8][8];
+        uint32_t acc[NO][8 * DW];
 #pragma unroll
-        for (int i = 0; i < 8; ++i)
+        for (int i = 0; i < NO; ++i)
 #pragma unroll
-            for (int y = 0; y < 8; ++y) acc[i][y] = 0;
-        switch (nout) {  // wave-uniform
-            case 0: break;
-            case 1: lh_ja_round<1, GT, PTR>(a, l, coef, i0, acc, tlo, thi); break;
-            case 2: lh_ja_round<2, GT, PTR>(a, l, coef, i0, acc, tlo, thi); break;
-            case 3: lh_ja_round<3, GT, PTR>(a, l, coef, i0, acc, tlo, thi); break;
-            case 4: lh_ja_round<4, GT, PTR>(a, l, coef, i0, acc, tlo, thi); break;
-            case 5: lh_ja_round<5, GT, PTR>(a, l, coef, i0, acc, tlo, thi); break;
-            case 6: lh_ja_round<6, GT, PTR>(a, l, coef, i0, acc, tlo, thi); break;
-            case 7: lh_ja_round<7, GT, PTR>(a, l, coef, i0, acc, tlo, thi); break;
-            default: lh_ja_round<8, GT, PTR>(a, l, coef, i0, acc, tlo, thi); break;
+            for (int y = 0; y < 8 * DW; ++y) acc[i][y] = 0;
+        bool ok = usable;
+        if (usable) {
+            lh_for_count<NO>(nout, [&](auto no) __attribute__((always_inline)) {
+                constexpr int N = decltype(no)::value;
+                if constexpr (N > 0) ok = lh_ja_round<N, DW, GT, PTR>(a, l, coef, i0, acc, tlo, thi);
+            });
         }
         // In place (decode): every wave of the workgroup has read every slot of this chunk
         // before any output overwrites one (the host runs a single round there).
         if (pl && ng > 1) __syncthreads();
         if (l.active) {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                if (i < nout) {
-                    uint8_t *dst = lh_ja_out<PTR>(a, l, pl ? (int)pl[16 + i0 + i] : i0 + i);
-#pragma unroll
-                    for (int y = 0; y < 8; ++y) *(lh_u32u *)(dst + (long long)y * a.sub) = acc[i][y];
-                }
-            }
-        }
-    }
-}
-}  // namespace
-
-template <bool PTR>
-__global__ void __launch_bounds__(1024) lh_apply_jump_kernel(lh::JumpApplyArgs a) {
-    uint32_t tlo, thi;
-    asm volatile(
-        "s_getpc_b64 s[92:93]\n"
-        "s_add_u32 s92, s92, lh_inv_gtab@rel32@lo+4\n"
-        "s_addc_u32 s93, s93, lh_inv_gtab@rel32@hi+12\n"
-        "s_mov_b32 %0, s92\n"
-        "s_mov_b32 %1, s93\n"
-        : "=s"(tlo), "=s"(thi)
-        :
-        : "s92", "s93", "scc");
-    if (a.jump_fallback || tlo > 0xFFFFFFFFu - 256u * 68u) {  // the table straddles a 4 GiB boundary
-        lh_apply_jump_body<false, PTR>(a, tlo, thi);              // (never seen), or the tests' switch
-        return;
-    }
-    lh_apply_jump_body<true, PTR>(a, tlo, thi);
-}
-
-// ---- two-dword form (a.dw == 2): a lane owns 8 bytes of every sub-block and a jump enters
-// lh_inv_gtab2, whose body c adds B(c) V to 16 accumulator words (tools/gen_inv_jump.py
-// render_global_table2) -- half the jumps per byte, at twice the table registers (60) and 4
-// outputs per wave.  ~150 VGPRs: at most 12 waves per workgroup (3 per SIMD).
-__global__ void lh_inv_gtab2_holder() { asm volatile(LH_INV_GTAB2_TEXT); }
-
-template <int N>
-__device__ __forceinline__ bool lh_mul_jump_g2(uint32_t (&acc)[4][16], const uint32_t (&tl)[16][2],
-                                               const uint32_t (&th)[16][2], const uint32_t (&t)[4], int r,
-                                               uint32_t tlo, uint32_t hi) {
-#if LH_GT_CHECK
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const uint32_t d = (uint32_t)__builtin_amdgcn_readlane((int)t[i], r) - tlo;
-        if (d >= 256u * 132u || d % 132u != 0u) return false;  // wave-uniform
-    }
-#else
-    (void)tlo;
-#endif
-#define LH_GT2_CASE(n)                                                                                       \
-    if constexpr (N == n)                                                                                    \
-        asm volatile(LH_INV_JUMPG2_##n##_ASM : LH_INV_JUMPG2_##n##_OUTS(acc) : LH_INV_JUMPG2_INS(tl, th, t),  \
-                     [r] "s"(r), [hi] "s"(hi) : "s92", "s93", "s94", "s95", "s97", "scc");
-    LH_GT2_CASE(1) LH_GT2_CASE(2) LH_GT2_CASE(3) LH_GT2_CASE(4)
-#undef LH_GT2_CASE
-#if LH_GT_CHECK
-    if (__builtin_amdgcn_s_getreg(1 | (27 << 6) | (0 << 11)) != 0) return false;
-#endif
-    return true;
-}
-
-namespace {
-typedef unsigned long long lh_u64u __attribute__((aligned(1)));
-
-__device__ __forceinline__ void lh_ja_load2(uint32_t (&d)[8][2], const uint8_t *col, int sub, bool active) {
-#pragma unroll
-    for (int b = 0; b < 8; ++b) d[b][0] = d[b][1] = 0;
-    if (active) {
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const unsigned long long v = *(const lh_u64u *)(col + (long long)b * sub);
-            d[b][0] = (uint32_t)v;
-            d[b][1] = (uint32_t)(v >> 32);
-        }
-    }
-}
-
-__device__ __forceinline__ void lh_ja_tables2(const uint32_t (&d)[8][2], uint32_t (&tl)[16][2],
-                                              uint32_t (&th)[16][2]) {
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        tl[0][h] = th[0][h] = 0;
-#pragma unroll
-        for (int q = 1; q < 16; ++q) {
-            const int low = __builtin_ctz(q), pre = q & (q - 1);
-            tl[q][h] = pre ? (tl[pre][h] ^ d[low][h]) : d[low][h];
-            th[q][h] = pre ? (th[pre][h] ^ d[4 + low][h]) : d[4 + low][h];
-        }
-    }
-}
-
-template <int N, bool PTR>
-__device__ __forceinline__ bool lh_ja_round2(const lh::JumpApplyArgs &a, const lh_ja_lane &l, const uint8_t *coef,
-                                             int i0, uint32_t (&acc)[4][16], uint32_t tlo, uint32_t thi) {
-    const int lane = threadIdx.x & 63;
-    bool ok = true;
-    for (int jq = 0; jq * 64 < a.n_in; ++jq) {
-        const int jc = jq * 64 + lane;
-        uint32_t t[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint32_t c = (i < N && jc < a.n_in) ? coef[(long long)(i0 + i) * a.n_in + jc] : 0u;
-            t[i] = tlo + c * 132u;
-        }
-        const int nj = a.n_in - jq * 64 < 64 ? a.n_in - jq * 64 : 64;
-        uint32_t cur[8][2];
-        lh_ja_load2(cur, lh_ja_col<PTR>(a, l, jq * 64), a.sub, l.active);
-        for (int jl = 0; jl < nj; ++jl) {  // wave-uniform
-            const int jn = jq * 64 + jl + 1 < a.n_in ? jq * 64 + jl + 1 : jq * 64 + jl;
-            uint32_t nxt[8][2];
-            lh_ja_load2(nxt, lh_ja_col<PTR>(a, l, jn), a.sub, l.active);
-            uint32_t tl[16][2], th[16][2];
-            lh_ja_tables2(cur, tl, th);
-            if (ok) ok = lh_mul_jump_g2<N>(acc, tl, th, t, jl, tlo, thi);
-#pragma unroll
-            for (int b = 0; b < 8; ++b) cur[b][0] = nxt[b][0], cur[b][1] = nxt[b][1];
-        }
-    }
-    return ok;
-}
-
-// gt: the table's address is usable.  The host launches this kernel only after
-// probe_jump_tables found lh_inv_gtab2 within one 4 GiB page; a failed check here (or in the
-// debug build's target check) poisons the outputs, so the parity tests fail loudly.
-template <bool PTR>
-__device__ __forceinline__ void lh_apply_jump2_body(const lh::JumpApplyArgs &a, bool gt, uint32_t tlo,
-                                                    uint32_t thi) {
-    const int lane = threadIdx.x & 63;
-    const int g = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), ng = (int)(blockDim.x >> 6);
-    lh_ja_lane l;
-    int c;
-    if (a.per_stripe) {
-        l.stripe = blockIdx.x / a.wps;
-        if (l.stripe >= a.stripes) return;  // workgroup-uniform
-        if (a.order) l.stripe = a.order[l.stripe];
-        c = (int)(blockIdx.x % a.wps) * 64 + lane;
-        l.active = c < a.nch;
-        c = l.active ? c : a.nch - 1;
-    } else {
-        const long long t = (long long)blockIdx.x * 64 + lane;
-        l.stripe = t / a.nch;
-        c = (int)(t - l.stripe * a.nch);
-        l.active = l.stripe < a.stripes;
-        if (!l.active) l.stripe = a.stripes - 1;
-    }
-    l.p = c == a.nch - 1 ? a.sub - 8 : 8 * c;  // (the last chunk overlaps its neighbour)
-    const uint8_t *pl = a.plan ? a.plan + l.stripe * a.plan_stride : nullptr;
-    const int n_out = pl ? pl[0] : a.n_out;
-    if (pl && n_out == 0) return;  // workgroup-uniform
-    const uint8_t *coef = a.coef + l.stripe * a.coef_stride;
-    const int rounds = (a.n_out + 4 * ng - 1) / (4 * ng);
-    for (int q = 0; q < rounds; ++q) {
-        const int i0 = 4 * (q * ng + g);
-        int nout = n_out - i0;
-        nout = nout < 0 ? 0 : (nout > 4 ? 4 : nout);  // wave-uniform
-        if (pl && nout == 0) return;  // (as lh_apply_jump_body)
-        uint32_t acc[4][16];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int y = 0; y < 16; ++y) acc[i][y] = 0;
-        bool ok = gt;
-        if (gt) {
-            switch (nout) {  // wave-uniform
-                case 0: break;
-                case 1: ok = lh_ja_round2<1, PTR>(a, l, coef, i0, acc, tlo, thi); break;
-                case 2: ok = lh_ja_round2<2, PTR>(a, l, coef, i0, acc, tlo, thi); break;
-                case 3: ok = lh_ja_round2<3, PTR>(a, l, coef, i0, acc, tlo, thi); break;
-                default: ok = lh_ja_round2<4, PTR>(a, l, coef, i0, acc, tlo, thi); break;
-            }
-        }
-        if (pl && ng > 1) __syncthreads();  // in place: every slot read before any is written
-        if (l.active) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
+            for (int i = 0; i < NO; ++i) {
                 if (i < nout) {
                     uint8_t *dst = lh_ja_out<PTR>(a, l, pl ? (int)pl[16 + i0 + i] : i0 + i);
 #pragma unroll
                     for (int y = 0; y < 8; ++y) {
-                        const unsigned long long v = ok ? ((unsigned long long)acc[i][2 * y + 1] << 32) | acc[i][2 * y]
-                                                        : 0xDEADBEEFDEADBEEFull;
-                        *(lh_u64u *)(dst + (long long)y * a.sub) = v;
+                        // the lane's DW words of sub-row y as one integer (DW 1: the word ORed with itself)
+                        typedef std::conditional_t<DW == 2, unsigned long long, uint32_t> W;
+                        typedef W Wu __attribute__((aligned(1)));
+                        const W v = ok ? (W)((unsigned long long)acc[i][DW * y + DW - 1] << (32 * (DW - 1)) | acc[i][DW * y])
+                                       : (W)0xDEADBEEFDEADBEEFull;
+                        *(Wu *)(dst + (long long)y * a.sub) = v;
                     }
                 }
             }
@@ -1361,35 +1247,36 @@ __device__ __forceinline__ void lh_apply_jump2_body(const lh::JumpApplyArgs &a, 
 }
 }  // namespace
 
+// A table that is not usable (never seen), or a.jump_fallback (tests), takes the in-asm table.
 template <bool PTR>
-__global__ void __launch_bounds__(768) lh_apply_jump2_kernel(lh::JumpApplyArgs a) {
+__global__ void __launch_bounds__(lh_jt<1>::kThreads) lh_apply_jump_kernel(lh::JumpApplyArgs a) {
     uint32_t tlo, thi;
-    asm volatile(
-        "s_getpc_b64 s[92:93]\n"
-        "s_add_u32 s92, s92, lh_inv_gtab2@rel32@lo+4\n"
-        "s_addc_u32 s93, s93, lh_inv_gtab2@rel32@hi+12\n"
-        "s_mov_b32 %0, s92\n"
-        "s_mov_b32 %1, s93\n"
-        : "=s"(tlo), "=s"(thi)
-        :
-        : "s92", "s93", "scc");
-    lh_apply_jump2_body<PTR>(a, tlo <= 0xFFFFFFFFu - 256u * 132u, tlo, thi);
+    LH_TABLE_ADDR(lh_inv_gtab, tlo, thi);
+    if (a.jump_fallback || tlo > lh_jt<1>::kMaxLo) {
+        lh_apply_jump_body<1, false, PTR>(a, true, tlo, thi);
+        return;
+    }
+    lh_apply_jump_body<1, true, PTR>(a, true, tlo, thi);
+}
+
+// The two-dword table, built as lh_inv_gtab (tools/gen_inv_jump.py render_global_table2): its
+// body c adds B(c) V to 16 accumulator words, at twice the table registers (60).  The host
+// launches the kernel only after jump_table2_usable found the table usable.
+__global__ void lh_inv_gtab2_holder() { asm volatile(LH_INV_GTAB2_TEXT); }
+
+template <bool PTR>
+__global__ void __launch_bounds__(lh_jt<2>::kThreads) lh_apply_jump2_kernel(lh::JumpApplyArgs a) {
+    uint32_t tlo, thi;
+    LH_TABLE_ADDR(lh_inv_gtab2, tlo, thi);
+    lh_apply_jump_body<2, true, PTR>(a, tlo <= lh_jt<2>::kMaxLo, tlo, thi);
 }
 
 // The low words of the two jump tables' addresses (out[0]: lh_inv_gtab, out[1]: lh_inv_gtab2),
-// read once per device: a table whose bodies straddle a 4 GiB boundary is not entered.
+// read once per device: a table that is not usable is not entered.
 __global__ void lh_jump_probe_kernel(uint32_t *out) {
-    uint32_t t1, t2;
-    asm volatile(
-        "s_getpc_b64 s[92:93]\n"
-        "s_add_u32 s92, s92, lh_inv_gtab@rel32@lo+4\n"
-        "s_mov_b32 %0, s92\n"
-        "s_getpc_b64 s[92:93]\n"
-        "s_add_u32 s92, s92, lh_inv_gtab2@rel32@lo+4\n"
-        "s_mov_b32 %1, s92\n"
-        : "=s"(t1), "=s"(t2)
-        :
-        : "s92", "s93", "scc");
+    uint32_t t1, t2, hi;
+    LH_TABLE_ADDR(lh_inv_gtab, t1, hi);
+    LH_TABLE_ADDR(lh_inv_gtab2, t2, hi);
     if (threadIdx.x == 0) {
         out[0] = t1;
         out[1] = t2;
@@ -1501,47 +1388,50 @@ hipError_t launch_apply_generic(const ApplyArgs &a, int W, hipStream_t st) {
     return hipGetLastError();
 }
 
-hipError_t launch_apply_jump(const JumpApplyArgs &a, hipStream_t st) {
-    // sub >= 4 (dword lanes); at most 16 waves of 8 outputs per workgroup; in place a single
-    // round (e_max <= 128 always holds: e_max = min(k, m) and k + m <= 256).
-    if (a.sub < 4 || a.n_out < 1 || a.n_in < 1 || a.nch < 1) return hipErrorInvalidValue;
+bool inv_fallback_forced() {
+    const char *fb = std::getenv("LONGHAIR_AMD_INV_FALLBACK");
+    return fb && std::atoi(fb);
+}
+
+// Waves per workgroup of the jump apply; 0: the shape does not fit the lane width.
+static int jump_apply_waves(const JumpApplyArgs &a) {
     if (a.dw == 2) {  // 4 outputs per wave, at most 12 waves, the rounds balanced over them
-        const int groups = (a.n_out + 3) / 4, rounds = (groups + 11) / 12, ng = (groups + rounds - 1) / rounds;
-        if (a.sub < 8 || (a.plan && rounds > 1)) return hipErrorInvalidValue;
-        const long long wgs = a.per_stripe ? (long long)a.stripes * a.wps : ((long long)a.stripes * a.nch + 63) / 64;
-        if (wgs <= 0) return hipSuccess;
-        if (wgs > 0x7FFFFFFF) return hipErrorInvalidValue;
-        JumpApplyArgs g = a;
-        if (!order_stripes(g.order, a.plan, a.plan_stride, a.per_stripe ? a.stripes : 0, a.n_out, st)) g.order = nullptr;
-        if (a.in_ptrs)
-            hipLaunchKernelGGL(lh_apply_jump2_kernel<true>, dim3((unsigned)wgs), dim3(64u * (unsigned)ng), 0, st, g);
-        else
-            hipLaunchKernelGGL(lh_apply_jump2_kernel<false>, dim3((unsigned)wgs), dim3(64u * (unsigned)ng), 0, st, g);
-        note_launch(a.in_ptrs ? "lh_apply_jump2_kernel(pointer table)" : "lh_apply_jump2_kernel");
-        return hipGetLastError();
+        constexpr int NO = lh_jt<2>::kOuts, NG = lh_jt<2>::kThreads / 64;
+        const int groups = (a.n_out + NO - 1) / NO, rounds = (groups + NG - 1) / NG;
+        return a.sub < 8 || (a.plan && rounds > 1) ? 0 : (groups + rounds - 1) / rounds;
     }
-    if (a.dw != 1) return hipErrorInvalidValue;
-    // Flat (encode) launches: a power-of-two number of waves per workgroup, further rounds for
-    // the remaining outputs, so whole workgroups fill a CU's 16 wave slots (124 VGPRs: 4 per
-    // SIMD); 7 waves left 2 slots idle.  k200/m56 generic encode 1.20-1.23 -> 1.10-1.11 ms
-    // (profiles/r5v_generic_pow2.txt).  In place: one round, every output's wave present.
-    int ng = (a.n_out + 7) / 8 < 16 ? (a.n_out + 7) / 8 : 16;
+    if (a.dw != 1) return 0;
+    // At most 16 waves of 8 outputs.  Flat (encode) launches: a power-of-two number of waves per
+    // workgroup, further rounds for the remaining outputs, so whole workgroups fill a CU's 16
+    // wave slots (124 VGPRs: 4 per SIMD); 7 waves left 2 slots idle.  k200/m56 generic encode
+    // 1.20-1.23 -> 1.10-1.11 ms (profiles/r5v_generic_pow2.txt).
+    constexpr int NO = lh_jt<1>::kOuts, NG = lh_jt<1>::kThreads / 64;
+    int ng = (a.n_out + NO - 1) / NO < NG ? (a.n_out + NO - 1) / NO : NG;
     if (!a.plan)
         while (ng & (ng - 1)) ng &= ng - 1;
-    if (a.plan && a.n_out > 8 * ng) return hipErrorInvalidValue;
+    return a.plan && a.n_out > NO * ng ? 0 : ng;
+}
+
+hipError_t launch_apply_jump(const JumpApplyArgs &a, hipStream_t st) {
+    // sub >= 4 (dword lanes); in place a single round, every output's wave present (e_max <= 128
+    // always holds: e_max = min(k, m) and k + m <= 256).
+    if (a.sub < 4 || a.n_out < 1 || a.n_in < 1 || a.nch < 1) return hipErrorInvalidValue;
+    const int ng = jump_apply_waves(a);
+    if (ng == 0) return hipErrorInvalidValue;
     const long long wgs = a.per_stripe ? (long long)a.stripes * a.wps : ((long long)a.stripes * a.nch + 63) / 64;
     if (wgs <= 0) return hipSuccess;
     if (wgs > 0x7FFFFFFF) return hipErrorInvalidValue;
     JumpApplyArgs g = a;
     if (!order_stripes(g.order, a.plan, a.plan_stride, a.per_stripe ? a.stripes : 0, a.n_out, st)) g.order = nullptr;
-    const char *fb = std::getenv("LONGHAIR_AMD_INV_FALLBACK");  // (tests: the in-asm table)
-    g.jump_fallback = fb && std::atoi(fb) ? 1 : 0;
-    if (a.in_ptrs)
-        hipLaunchKernelGGL(lh_apply_jump_kernel<true>, dim3((unsigned)wgs), dim3(64u * (unsigned)ng), 0, st, g);
-    else
-        hipLaunchKernelGGL(lh_apply_jump_kernel<false>, dim3((unsigned)wgs), dim3(64u * (unsigned)ng), 0, st, g);
-    note_launch(g.jump_fallback ? (a.in_ptrs ? "lh_apply_jump_kernel(pointer table, fallback)" : "lh_apply_jump_kernel(fallback)")
-                                : (a.in_ptrs ? "lh_apply_jump_kernel(pointer table)" : "lh_apply_jump_kernel"));
+    const bool two = a.dw == 2, ptr = a.in_ptrs != nullptr;
+    g.jump_fallback = (two ? lh_jt<2>::kAsmFallback : lh_jt<1>::kAsmFallback) && inv_fallback_forced();
+    const auto kernel = two ? (ptr ? lh_apply_jump2_kernel<true> : lh_apply_jump2_kernel<false>)
+                            : (ptr ? lh_apply_jump_kernel<true> : lh_apply_jump_kernel<false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)wgs), dim3(64u * (unsigned)ng), 0, st, g);
+    const std::string name = two ? "lh_apply_jump2_kernel" : "lh_apply_jump_kernel";
+    note_launch((name + (g.jump_fallback ? (ptr ? "(pointer table, fallback)" : "(fallback)")
+                                         : (ptr ? "(pointer table)" : "")))
+                    .c_str());
     return hipGetLastError();
 }
 
@@ -1556,7 +1446,7 @@ bool jump_table2_usable(int device) {
     if (hipMalloc(&d_out, 8) == hipSuccess) {
         hipLaunchKernelGGL(lh_jump_probe_kernel, dim3(1), dim3(64), 0, nullptr, d_out);
         ok = hipGetLastError() == hipSuccess && hipMemcpy(h, d_out, 8, hipMemcpyDeviceToHost) == hipSuccess &&
-             h[1] <= 0xFFFFFFFFu - 256u * 132u;
+             h[1] <= lh_jt<2>::kMaxLo;
         (void)hipFree(d_out);
     }
     known[device] = ok;
@@ -1574,9 +1464,8 @@ hipError_t launch_inverse(const InverseArgs &a, hipStream_t st) {
     // decode 3.56 -> 3.51 ms packed, k200/m56 0.583 -> 0.567 spread).
     // LONGHAIR_AMD_INV_FALLBACK=1: the in-asm table inside the same kernel (tests).
     InverseArgs g = a;
-    const char *fb = std::getenv("LONGHAIR_AMD_INV_FALLBACK");
     g.pack = a.e_max <= 32 ? 1 : 0;
-    g.jump_fallback = fb && std::atoi(fb) ? 1 : 0;
+    g.jump_fallback = inv_fallback_forced();
     // Two consecutive 2 KiB chunks of a stripe per workgroup, the tile pipeline carried across
     // them, so the pipeline's start (plan, jump targets, first tile's DMA) is paid once per
     // pair (profiles/r4k_tune_*_inv_chunks.txt: k200/m56 decode 0.665 -> 0.617 ms with 2, 0.635

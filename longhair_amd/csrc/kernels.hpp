@@ -191,6 +191,9 @@ hipError_t launch_apply_generic(const ApplyArgs &a, int W, hipStream_t st);
 hipError_t launch_apply_jump(const JumpApplyArgs &a, hipStream_t st);
 // lh_inv_gtab2 lies within one 4 GiB page on `device` (probed once; dw 2 only then)
 bool jump_table2_usable(int device);
+// LONGHAIR_AMD_INV_FALLBACK is set and non-zero (tests): phase B and the one-dword jump apply
+// take the in-asm table, and no batch takes two-dword lanes
+bool inv_fallback_forced();
 hipError_t launch_frame(const FrameArgs &a, hipStream_t st);
 hipError_t launch_xor_reduce(const XorArgs &a, hipStream_t st);
 hipError_t launch_scatter(const ScatterArgs &a, hipStream_t st);

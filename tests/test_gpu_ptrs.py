@@ -230,6 +230,16 @@ def test_decode_batch_ptrs(lh, oracle, k, m, nbytes, stripes, form):
         _gaps_untouched(pool2, place2)
 
 
+@pytest.mark.parametrize("check", [test_encode_batch_ptrs, test_decode_batch_ptrs], ids=["encode", "decode"])
+def test_batch_ptrs_in_asm_table(lh, oracle, monkeypatch, check):
+    """The one-dword jump apply through the pointer table with the in-asm table
+    (LONGHAIR_AMD_INV_FALLBACK=1 on the generic path), flat and in place: the checks of the two
+    tests above at k 40, m 4, sub 517 -- three workgroups per stripe, the last lane shifted back."""
+    monkeypatch.setenv("LONGHAIR_AMD_PATH", "generic")
+    monkeypatch.setenv("LONGHAIR_AMD_INV_FALLBACK", "1")
+    check(lh, oracle, 40, 4, 4136, 8, "lh_apply_jump_kernel(pointer table, fallback)")
+
+
 MIXED_PTRS = [
     (29, 4, 1296, 50, "lh_jit_decode_fused(pointer table)"),
     (29, 8, 1296, 24, "lh_jit_decode(pointer table)"),
