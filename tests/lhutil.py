@@ -120,6 +120,146 @@ def erasure_case(seed, k, m, e, shuffle=True):
     return slots, rows
 
 
+# ------------------------------------------------------------- deterministic erasure patterns
+# A pattern is (E, R): the erased originals and the recovery rows that stand in for them, two
+# ascending tuples of the same length e.  `placements` lays one pattern out over the k slots in
+# up to five ways; `exhaustive_patterns` is every pattern of a small code, `designed_patterns` a
+# net over the edges of a code too large to enumerate.  Nothing here draws an unseeded number
+# (tests/test_lhutil_patterns.py).
+PLACEMENTS = "abcde"
+EDGES = (0, 1, 2, 31, 32, 62, 63, 64, 65, 126, 127, 128, 129)
+
+
+def edges(n):
+    """The positions of [0, n) at which the kernels change lane, wave or pass."""
+    return sorted({v for v in EDGES + (n - 3, n - 2, n - 1) if 0 <= v < n})
+
+
+def placements(k, E, R, seed, keep=PLACEMENTS, labels=False):
+    """The distinct slot layouts of one pattern, as `erasure_case` returns them ((slots, rows);
+    with `labels` (label, slots, rows)), in this order:
+      a  recovery blocks in the erased slots, R ascending;   b  the same, R descending;
+      c  survivors in order, then the recovery blocks;       d  recovery blocks, then survivors;
+      e  one permutation of c, seeded by `seed`.
+    `keep` names the layouts wanted; duplicates of an earlier layout are dropped."""
+    E, R = sorted(int(x) for x in E), sorted(int(j) for j in R)
+    assert len(E) == len(R) and len(set(E)) == len(E) and len(set(R)) == len(R)
+    assert all(0 <= x < k for x in E)
+    surv = [("d", x) for x in range(k) if x not in set(E)]
+    rec = [("r", j) for j in R]
+    at = {x: i for i, x in enumerate(E)}
+    c = surv + rec
+    perm = np.random.Generator(np.random.PCG64(seed)).permutation(k).tolist()
+    forms = {
+        "a": [("r", R[at[x]]) if x in at else ("d", x) for x in range(k)],
+        "b": [("r", R[len(R) - 1 - at[x]]) if x in at else ("d", x) for x in range(k)],
+        "c": c,
+        "d": rec + surv,
+        "e": [c[i] for i in perm],
+    }
+    out, seen = [], set()
+    for label in PLACEMENTS:
+        slots = forms[label]
+        if label not in keep or tuple(slots) in seen:
+            continue
+        seen.add(tuple(slots))
+        rows = [x if kind == "d" else k + x for kind, x in slots]
+        out.append((label, slots, rows) if labels else (slots, rows))
+    return out
+
+
+def exhaustive_patterns(k, m):
+    """Every (E, R) with |E| = |R| = e, e = 0..min(k, m): C(k + m, k) of them (Vandermonde)."""
+    import itertools
+    return [(E, R) for e in range(min(k, m) + 1)
+            for E in itertools.combinations(range(k), e) for R in itertools.combinations(range(m), e)]
+
+
+def designed_patterns(k, m):
+    """Patterns for a code too large to enumerate, duplicates dropped, in this order: the empty
+    pattern; every single erasure (x, j) (all x and j when k * m <= 1024, else edges(k) x
+    edges(m)); for e = 1..e_max the four ladders (first / last e originals x first / last e
+    rows), one evenly strided pattern (E = floor(i k / e), R = floor(i m / e)) and, from e = 2,
+    the same originals with the rows spread from row 0 to row m - 1 inclusive
+    (R = floor(i (m - 1) / (e - 1))), so that row 0 meets row m - 1 at every e and not only at
+    e = m."""
+    e_max = min(k, m)
+    out = [((), ())]
+    xs, js = (range(k), range(m)) if k * m <= 1024 else (edges(k), edges(m))
+    out += [((x,), (j,)) for x in xs for j in js]
+    for e in range(1, e_max + 1):
+        first_x, last_x = tuple(range(e)), tuple(range(k - e, k))
+        first_j, last_j = tuple(range(e)), tuple(range(m - e, m))
+        out += [(first_x, first_j), (last_x, last_j), (first_x, last_j), (last_x, first_j)]
+        E = tuple(i * k // e for i in range(e))
+        if len(set(E)) == e:
+            R = tuple(i * m // e for i in range(e))
+            out.append((E, R if len(set(R)) == e else first_j))
+            if e >= 2:
+                R = tuple(i * (m - 1) // (e - 1) for i in range(e))
+                if len(set(R)) == e:
+                    out.append((E, R))
+    return list(dict.fromkeys(out))
+
+
+def pattern_cases(k, m, patterns, seed, keep=PLACEMENTS):
+    """Every pattern x placement, in generation order: a list of (E, R, label, slots, rows).
+    Pattern i's permuted layout is seeded by (seed, i)."""
+    return [(E, R, label, slots, rows) for i, (E, R) in enumerate(patterns)
+            for label, slots, rows in placements(k, E, R, seed * 1000003 + i, keep, labels=True)]
+
+
+def pattern_data(k, bytes_, stripes, seed, pool=32):
+    """The data stripes of `pattern_batch`, uint8 [min(pool, stripes), k, bytes]: stripe s of
+    the batch was encoded from entry s % len."""
+    n = max(1, min(pool, stripes))
+    return fill(seed, n * k * bytes_).reshape(n, k, bytes_)
+
+
+def pattern_batch(codec, k, m, bytes_, cases, seed, pool=32):
+    """The received stripes of `pattern_cases`: (blocks uint8 [S, k, bytes], rows uint8 [S, k]).
+    Stripe s takes data stripe s % pool of `fill(seed, ...)` and its recovery blocks from
+    codec.encode, so neighbouring stripes hold different bytes."""
+    data = pattern_data(k, bytes_, len(cases), seed, pool)
+    n = data.shape[0]
+    both = np.empty((n, k + m, bytes_), dtype=np.uint8)
+    both[:, :k] = data
+    for p in range(n):
+        rc, rec = codec.encode(k, m, data[p], bytes_)
+        assert rc == 0, (k, m, bytes_, rc)
+        both[p, k:] = rec.reshape(m, bytes_)
+    rows = np.array([c[4] for c in cases], dtype=np.uint8).reshape(len(cases), k)
+    blocks = both[(np.arange(len(cases)) % n)[:, None], rows.astype(np.intp)]
+    return blocks, rows
+
+
+_BLOCK_DT = np.dtype({"names": ["data", "row"], "formats": ["<u8", "u1"], "offsets": [0, 8],
+                      "itemsize": ctypes.sizeof(Block)})
+
+
+def decode_all(codec, k, m, blocks, rows, bytes_):
+    """codec.decode of every stripe of (blocks [S, k, bytes], rows [S, k]), the inputs left
+    alone: (return codes int32 [S], rows out uint8 [S, k], blocks out uint8 [S, k, bytes])."""
+    out = np.array(blocks, dtype=np.uint8, order="C")
+    stripes = out.shape[0]
+    assert out.shape == (stripes, k, bytes_)
+    tab = np.zeros((stripes, k), dtype=_BLOCK_DT)
+    tab["data"] = out.ctypes.data + (np.arange(stripes * k, dtype=np.uint64) * np.uint64(bytes_)).reshape(stripes, k)
+    tab["row"] = rows
+    rcs = np.empty(stripes, dtype=np.int32)
+    for s in range(stripes):
+        rcs[s] = codec._dec(k, m, ctypes.c_void_p(tab.ctypes.data + s * tab.strides[0]), bytes_)
+    return rcs, np.ascontiguousarray(tab["row"]), out
+
+
+def pattern_digest(rcs, rows_out, blocks_out):
+    """The fixture digest of a shape's decoded cases: h64 over the return codes (one signed
+    byte each), every rows-out and every block, in generation order."""
+    return h64(np.concatenate([np.asarray(rcs).astype(np.int8).view(np.uint8).reshape(-1),
+                               np.asarray(rows_out, dtype=np.uint8).reshape(-1),
+                               np.asarray(blocks_out, dtype=np.uint8).reshape(-1)]))
+
+
 # ------------------------------------------------------------------ invalid stripes
 # include/cauchy_256_batch.h: a stripe whose rows hold a duplicate or a row >= k + m is
 # invalid (status -1, left untouched).  `invalidate_rows` breaks a valid stripe in one named

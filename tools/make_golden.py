@@ -10,6 +10,13 @@ Runs only in the build container: it loads oracle/_ref/liblonghair_ref.so, which
   encode_full.json   a few tiny cases with full input and output bytes (hex).
   decode_cases.json  decode scenarios (block order, rows) -> return code, final rows and
                      the digest of every block buffer after decode.
+  decode_patterns.json  one record per code of tests/test_gpu_patterns.py CODES: every
+                     deterministic erasure pattern x placement of the code (lhutil
+                     exhaustive_patterns / designed_patterns, placements) decoded at 8-byte
+                     blocks, as {k, m, set ("x" exhaustive, "d" designed), placements, bytes,
+                     seed, patterns, stripes, h64}.  h64 is lhutil.pattern_digest: one digest
+                     over every return code, every rows-out and every block, in generation
+                     order (tests/test_decode_patterns.py holds the C oracle to it).
 
 Inputs are regenerated from tests/lhutil.fill(seed, n); digests are tests/lhutil.h64.
 """
@@ -127,9 +134,27 @@ def decode_cases(ref):
     return cases
 
 
+def decode_patterns(ref):
+    import test_gpu_patterns as tp
+    codes = []
+    for k, m, kind, keep in tp.CODES:
+        cases, rcs, rows_out, blocks_out = tp.cpu_decode(ref, k, m, kind)
+        codes.append({"k": k, "m": m, "set": kind, "placements": keep, "bytes": tp.CPU_BYTES,
+                      "seed": tp.seed_of(k, m), "patterns": len(tp.patterns_of(k, m, kind)),
+                      "stripes": len(cases), "h64": lhutil.pattern_digest(rcs, rows_out, blocks_out)})
+    return codes
+
+
 def main():
     ref = lhutil.RefLib()
     os.makedirs(lhutil.GOLDEN, exist_ok=True)
+    pat = decode_patterns(ref)
+    with open(os.path.join(lhutil.GOLDEN, "decode_patterns.json"), "w") as f:
+        f.write('{"spec":"see tools/make_golden.py","codes":[\n' +
+                ",\n".join(json.dumps(c, separators=(",", ":")) for c in pat) + "\n]}\n")
+    print("decode_patterns", len(pat), "codes,", sum(c["stripes"] for c in pat), "stripes")
+    if sys.argv[1:] == ["decode_patterns"]:
+        return
     grid = encode_grid(ref)
     json.dump({"spec": "rows: [k, m, bytes, seed, rc, h64(recovery)]", "cases": grid},
               open(os.path.join(lhutil.GOLDEN, "encode_grid.json"), "w"), separators=(",", ":"))

@@ -30,6 +30,11 @@ KNOB_JOBS = [((29, 4, 1296), {"LONGHAIR_AMD_JIT_DEFINES": "LH_LDS=0,LH_PF=2,LH_N
              ((29, 4, 1296), {"LONGHAIR_AMD_JIT_DEFINES": "LH_CPS=1"}),
              ((29, 4, 1296), {"LONGHAIR_AMD_JIT_DEFINES": "LH_CPS=3,LH_WPB=2,LH_WGCU=2"})]
 
+# Modules of the erasure-pattern batches (tests/test_gpu_patterns.py) that no list above holds:
+# the exhaustive (4, 4) set through the separate planner and lh_jit_decode.  (Its other shapes
+# are sweep, boundary, family and pointer-table shapes; it runs with LONGHAIR_AMD_JIT_COMPILE=0.)
+PATTERN_JOBS = [((4, 4, 8), {"LONGHAIR_AMD_NO_FUSED_PLAN": "1"})]
+
 
 def lds_sample(n, seed=606):
     """A seeded sample of n shapes served by the LDS-staged register networks:
@@ -129,6 +134,8 @@ def main():
             have |= set(sweep_shapes(tb))
             # the specialised-kernel parity sample (test_specialised_sample), slowest first
             jobs_list += [(sh, None) for sh in sorted(tb.JIT_SAMPLE, key=lambda s: -s[0] * s[1]) if sh not in have]
+            # the erasure-pattern batches' knob module (test_gpu_patterns.py), beside the shape's own
+            jobs_list += [(s, ("dec", env)) for s, env in PATTERN_JOBS]
             # the encode and decode modules of a shape in separate processes
             split = []
             for sh, part in jobs_list:
