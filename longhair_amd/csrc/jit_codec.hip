@@ -451,6 +451,49 @@ struct lh_unroll_encode<LH_K> {
     __device__ __forceinline__ static void run(lh_word (&)[LH_M][8], lh_word (&)[LH_PF][8], const lh_esrc &) {}
 };
 
+// 8-byte lanes whose last chunk of a sub-block is partial (the LDS-DMA forms below):
+typedef unsigned int lh_u32x2a __attribute__((ext_vector_type(2)));
+// Bytes [S, S + 8) of the 16 little-endian bytes (a, b).
+template <int S>
+__device__ __forceinline__ lh_word lh_funnel(unsigned a0, unsigned a1, unsigned b0, unsigned b1) {
+    lh_word w;
+    if constexpr (S == 0) {
+        w.v[0] = a0; w.v[1] = a1;
+    } else if constexpr (S == 4) {
+        w.v[0] = a1; w.v[1] = b0;
+    } else if constexpr (S < 4) {
+        w.v[0] = __builtin_amdgcn_alignbyte(a1, a0, S); w.v[1] = __builtin_amdgcn_alignbyte(b0, a1, S);
+    } else if constexpr (S == 8) {
+        w.v[0] = b0; w.v[1] = b1;
+    } else {
+        w.v[0] = __builtin_amdgcn_alignbyte(b0, a1, S - 4); w.v[1] = __builtin_amdgcn_alignbyte(b1, b0, S - 4);
+    }
+    return w;
+}
+__device__ __forceinline__ unsigned lh_row_shr1(unsigned v) {  // lane i <- lane i - 1 within a DPP row of 16
+    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);
+}
+// The 8 sub-row words of one output row to memory, sub-row y at dst + y * sub.  The last lane
+// of a stripe keeps its chunk's last VL bytes and stores [sub - 8, sub), funnelled with the
+// previous lane's word.  ORDERED: the stores kept in address order: a line two neighbouring
+// sub-rows share then gets both halves back to back; reordered by the scheduler, the
+// non-temporal halves left as partial-line writes, +14 MB per k29/m4 launch
+// (profiles/r10x/r10y PMC).
+template <int VL, bool ORDERED>
+__device__ __forceinline__ void lh_store_row(unsigned char *dst, int sub, const lh_word (&o)[8], bool last) {
+#pragma unroll
+    for (int y = 0; y < 8; ++y) {
+        lh_word w = o[y];
+        if constexpr (VL != 8) {
+            const lh_word f = lh_funnel<VL>(lh_row_shr1(w.v[0]), lh_row_shr1(w.v[1]), w.v[0], w.v[1]);
+            w.v[0] = last ? f.v[0] : w.v[0];
+            w.v[1] = last ? f.v[1] : w.v[1];
+        }
+        lh_store(dst + y * sub, w);
+        if constexpr (ORDERED) asm volatile("" ::: "memory");
+    }
+}
+
 // ---------------------------------------------------------------- LDS-DMA column loads
 // LH_LDS = 1 (jit.cpp, whole stripes per wave with 8-byte lanes and 16-byte-multiple blocks,
 // e.g. k29/m4/1296): the column x of the wave's LH_SPW stripes is fetched as aligned 16-byte
@@ -484,24 +527,6 @@ struct lh_unroll_encode<LH_K> {
 #define LH_VLAST (LH_SUB - 8 * (LH_NCH - 1))      // valid bytes of the last chunk of a sub-block
 // (ring padding: only when the image ends within 16 bytes of its slot's end)
 #define LH_LPAD ((LH_SPW * LH_BYTES + 16 > LH_LQ * 1024) ? 16 : 0)
-typedef unsigned int lh_u32x2a __attribute__((ext_vector_type(2)));
-// Bytes [S, S + 8) of the 16 little-endian bytes (a, b).
-template <int S>
-__device__ __forceinline__ lh_word lh_funnel(unsigned a0, unsigned a1, unsigned b0, unsigned b1) {
-    lh_word w;
-    if constexpr (S == 0) {
-        w.v[0] = a0; w.v[1] = a1;
-    } else if constexpr (S == 4) {
-        w.v[0] = a1; w.v[1] = b0;
-    } else if constexpr (S < 4) {
-        w.v[0] = __builtin_amdgcn_alignbyte(a1, a0, S); w.v[1] = __builtin_amdgcn_alignbyte(b0, a1, S);
-    } else if constexpr (S == 8) {
-        w.v[0] = b0; w.v[1] = b1;
-    } else {
-        w.v[0] = __builtin_amdgcn_alignbyte(b0, a1, S - 4); w.v[1] = __builtin_amdgcn_alignbyte(b1, b0, S - 4);
-    }
-    return w;
-}
 // The lane's word of sub-block B from a ring slot: `lo` its chunk's offset in the image
 // (stripe * bytes + 8 c), `lo8` = lo + 8 hidden from the compiler so the pair stays two
 // ds_read_b64 (2 LDS cycles each) instead of one ds_read2_b64 (8).
@@ -524,9 +549,6 @@ __device__ __forceinline__ void lh_slot_col(lh_word (&d)[8], const unsigned char
         d[B] = lh_slot_word<B>(slot, lo, lo8);
         lh_slot_col<B + 1>(d, slot, lo, lo8);
     }
-}
-__device__ __forceinline__ unsigned lh_row_shr1(unsigned v) {  // lane i <- lane i - 1 within a DPP row of 16
-    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);
 }
 typedef unsigned int lh_u32x4a __attribute__((ext_vector_type(4)));
 // An 8-byte word into LDS at an address A (mod 8) bytes past an 8-byte boundary, in naturally
@@ -759,16 +781,7 @@ __device__ __forceinline__ void lh_encode_wave_lds(long long wave, const unsigne
 #pragma unroll
     for (int r = 0; r < LH_M; ++r) {
         unsigned char *o = (unsigned char *)S.pt[sl * LH_LPR + LH_K + r] + p;
-#pragma unroll
-        for (int y = 0; y < 8; ++y) {
-            lh_word w = acc[r][y];
-            if constexpr (LH_VLAST != 8) {
-                const lh_word f = lh_funnel<LH_VLAST>(lh_row_shr1(w.v[0]), lh_row_shr1(w.v[1]), w.v[0], w.v[1]);
-                w.v[0] = last ? f.v[0] : w.v[0];
-                w.v[1] = last ? f.v[1] : w.v[1];
-            }
-            lh_store(o + y * LH_SUB, w);
-        }
+        lh_store_row<LH_VLAST, false>(o, LH_SUB, acc[r], last);
     }
 }
 
@@ -878,21 +891,7 @@ __device__ __forceinline__ void lh_encode_wave_cps(long long wave, const unsigne
     const int p = last ? LH_SUB - 8 : 8 * c;
     unsigned char *o = out + (s0 + sl) * out_stride + p;
 #pragma unroll
-    for (int r = 0; r < LH_M; ++r)
-#pragma unroll
-        for (int y = 0; y < 8; ++y) {
-            lh_word w = acc[r][y];
-            if constexpr (LH_VLAST != 8) {
-                const lh_word f = lh_funnel<LH_VLAST>(lh_row_shr1(w.v[0]), lh_row_shr1(w.v[1]), w.v[0], w.v[1]);
-                w.v[0] = last ? f.v[0] : w.v[0];
-                w.v[1] = last ? f.v[1] : w.v[1];
-            }
-            lh_store(o + (long long)r * LH_BYTES + y * LH_SUB, w);
-            // (stores kept in address order: a line two neighbouring sub-rows share then gets
-            // both halves back to back; reordered by the scheduler, the non-temporal halves
-            // left as partial-line writes, +14 MB per k29/m4 launch, profiles/r10x/r10y PMC)
-            asm volatile("" ::: "memory");
-        }
+    for (int r = 0; r < LH_M; ++r) lh_store_row<LH_VLAST, true>(o + (long long)r * LH_BYTES, LH_SUB, acc[r], last);
 }
 #endif  // LH_CPS
 
@@ -1052,7 +1051,9 @@ struct lh_unroll_fam {
     }
 };
 // The recovery blocks from the accumulators, per lane; the last lane of a stripe keeps the
-// sub-block's last VL (= sub - 8 (nch - 1)) bytes, funnelled with its neighbour's word.
+// sub-block's last VL (= sub - 8 (nch - 1)) bytes, funnelled with its neighbour's word.  (The
+// stores of lh_store_row<VL, true>, written out: through that call this kernel, at 252 VGPRs,
+// compiles to other instructions)
 template <int VL>
 __device__ __forceinline__ void lh_fam_store(const lh_word (&acc)[LH_M][8], unsigned char *o, const lh_fam &F, bool last) {
 #pragma unroll
@@ -1385,19 +1386,18 @@ __device__ __forceinline__ void lh_dec_phase_a(lh_word (&v)[LH_M][8], lh_word (&
 
 // Phase B: D_{E_i} = sum_r B(coef[i][r]) V_r with the per-stripe inverse, by Horner over
 // the coefficient bits: B(c) v = B(2)(...B(2)(c_7 v)...) + c_0 v, one v_bitop3 masked XOR
-// per (row, bit, sub-row); the recovered blocks go to the plan's output slots.
-struct lh_dsrc;
-__device__ __forceinline__ void lh_dec_phase_b(const lh_word (&v)[LH_M][8], const lh_plan_regs &pr,
-                                               unsigned char *base, bool last, const lh_dsrc &S, int soff) {
-    (void)last;
-    (void)S;
-    (void)soff;
+// per (row, bit, sub-row); recovered block i goes to the plan's output slot i, the lane's chunk
+// of which is `dst(slot)`, sub-row y at + y * sub.  The staged kernels' last lane of a stripe
+// (`last`) keeps its chunk's last VL bytes and stores [sub - 8, sub), funnelled with the
+// previous lane's word (VL = 8: whole words, no funnel); ORDERED: the stores kept in address
+// order, as lh_store_row's.
+template <int VL, bool ORDERED, class DST>
+__device__ __forceinline__ void lh_phase_b(const lh_word (&v)[LH_M][8], const lh_plan_regs &pr, bool last, int sub,
+                                           DST dst) {
     const int e = pr.e;
-    const unsigned int(&coefw)[LH_NCOEF] = pr.coefw;
-    const unsigned int(&outw)[LH_NOUT] = pr.outw;
 #pragma unroll
     for (int i = 0; i < LH_EMAX; ++i) {
-        if (i < e) {
+        if (i < e) {  // stripe-uniform: the funnel's source lane is active too
             lh_word o[8];
 #pragma unroll
             for (int y = 0; y < 8; ++y)
@@ -1418,7 +1418,7 @@ __device__ __forceinline__ void lh_dec_phase_b(const lh_word (&v)[LH_M][8], cons
                     const int idx = i * LH_M + r;
                     // 0 or ~0: bit t of coef[i][r], sign-extended (one v_bfe_i32)
                     const unsigned int mask =
-                        (unsigned int)((int)(coefw[idx / 4] << (31 - (8 * (idx % 4) + t))) >> 31);
+                        (unsigned int)((int)(pr.coefw[idx / 4] << (31 - (8 * (idx % 4) + t))) >> 31);
 #pragma unroll
                     for (int y = 0; y < 8; ++y)
 #pragma unroll
@@ -1430,13 +1430,10 @@ __device__ __forceinline__ void lh_dec_phase_b(const lh_word (&v)[LH_M][8], cons
                 lh_pin8(o);
 #endif
             }
-#if LH_PTR
-            unsigned char *dst = (unsigned char *)S.pt[LH_BYTE(outw, i)] + soff;  // soff: the lane's store offset
-#else
-            unsigned char *dst = base + (long long)LH_BYTE(outw, i) * LH_BYTES;
-#endif
-#pragma unroll
-            for (int y = 0; y < 8; ++y) lh_store(dst + y * LH_SUB, o[y]);
+            unsigned char *d = dst((int)LH_BYTE(pr.outw, i));
+            // (Holding a block's last sub-row back to store it right before the next block's
+            // first measured slower, write bytes unchanged: profiles/r10w_store_order_k29m4.txt.)
+            lh_store_row<VL, ORDERED>(d, sub, o, last);
         }
     }
 }
@@ -1481,12 +1478,11 @@ __device__ __forceinline__ void lh_decode_body(const lh_lane &l, long long wave,
         prep(pr);
         lh_dec_phase_a<PF>(v, ring, pr, S);
     }
-#if LH_BUF
-    lh_dec_phase_b(v, pr, blocks + l.stripe * stripe_stride + l.p, l.last, S, S.lbase - l.p);
-#elif LH_PTR
-    lh_dec_phase_b(v, pr, nullptr, l.last, S, l.p);
+#if LH_PTR
+    lh_phase_b<8, false>(v, pr, false, LH_SUB, [&](int slot) { return (unsigned char *)S.pt[slot] + l.p; });
 #else
-    lh_dec_phase_b(v, pr, blocks + l.stripe * stripe_stride + l.p, l.last, S, 0);
+    unsigned char *base = blocks + l.stripe * stripe_stride + l.p;
+    lh_phase_b<8, false>(v, pr, false, LH_SUB, [&](int slot) { return base + (long long)slot * LH_BYTES; });
 #endif
 }
 
@@ -1790,6 +1786,7 @@ struct lh_dmoff {  // scratch offset of column X's slot byte
     static constexpr int v = D::rec ? LH_SR_REC + D::r : LH_SR_SRC + D::x;
 };
 struct lh_dldsrc {
+    static constexpr int nq = LH_LQ, slot_bytes = LH_LQ * 1024;  // DMA instructions per column; ring slot
 #if LH_PTR
     const unsigned long long *pt;  // LDS: the wave's pointer rows [stripe][LH_K + 1]
     int prow[LH_LQ];               // DMA chunk q: its stripe's row in pt
@@ -1801,23 +1798,15 @@ struct lh_dldsrc {
     int jsc[LH_LQ];   // ... its stripe's scratch offset, or -1: nothing to do there
     const unsigned char *scr;  // the wave's scratch (LDS)
     unsigned char *ring;
-    template <int X>
-    __device__ __forceinline__ void slots(unsigned (&sv)[LH_LQ]) const {
-#pragma unroll
-        for (int q = 0; q < LH_LQ; ++q) {  // (unconditional read: no branch per chunk)
-            const unsigned b = scr[(jsc[q] & 0x7FFFFFFF) + lh_dmoff<X>::v];
-            sv[q] = jsc[q] < 0 ? 0xFFu : b;
-        }
-    }
     __device__ __forceinline__ void issue(const unsigned (&sv)[LH_LQ], int slot) const {
 #pragma unroll
         for (int q = 0; q < LH_LQ; ++q)
 #if LH_PTR
             lh_dma16<LH_LDS_NT_DEC>((const unsigned char *)pt[prow[q] + (sv[q] == 0xFFu ? LH_K : (int)sv[q])] + joff[q],
-                                    ring + slot * (LH_LQ * 1024) + q * 1024);
+                                    ring + slot * slot_bytes + q * 1024);
 #else
             __builtin_amdgcn_raw_ptr_buffer_load_lds(
-                rs, (__attribute__((address_space(3))) void *)(ring + slot * (LH_LQ * 1024) + q * 1024), 16,
+                rs, (__attribute__((address_space(3))) void *)(ring + slot * slot_bytes + q * 1024), 16,
                 sv[q] == 0xFFu ? (int)0x80000000 : joff[q] + (int)sv[q] * LH_BYTES, 0, 0, LH_LDS_NT_DEC ? 2 : 0);
 #endif
     }
@@ -1833,122 +1822,68 @@ struct lh_dldsrc {
 #if LH_LDG < 1 || LH_LDG >= LH_LD
 #error "LH_LDG: 1 <= LH_LDG < LH_LD"
 #endif
+// The staged ring of the fused decode, over its column source SRC (lh_dldsrc, or the block-size
+// family's lh_fdsrc: SRC::nq DMA instructions per column into slots of SRC::slot_bytes).
+// Column X's slot byte of every DMA chunk's stripe, from the plan's maps in the wave's scratch.
+template <int X, class SRC>
+__device__ __forceinline__ void lh_dslot(const SRC &S, unsigned (&sv)[SRC::nq]) {
+#pragma unroll
+    for (int q = 0; q < SRC::nq; ++q) {  // (unconditional read: no branch per chunk)
+        const unsigned b = S.scr[(S.jsc[q] & 0x7FFFFFFF) + lh_dmoff<X>::v];
+        sv[q] = S.jsc[q] < 0 ? 0xFFu : b;
+    }
+}
 // Columns C .. C + N - 1 (those that exist): their slot maps read into sv[0 .. N - 1] (before
 // the wait of the column that ends the group), then their DMAs issued into their slots.
-template <int C, int N>
-__device__ __forceinline__ void lh_dslots(const lh_dldsrc &S, unsigned (&sv)[LH_LDG][LH_LQ]) {
+template <int C, int N, class SRC>
+__device__ __forceinline__ void lh_dslots(const SRC &S, unsigned (&sv)[LH_LDG][SRC::nq]) {
     if constexpr (N > 0 && C < LH_DCOLS) {
-        S.slots<C>(sv[LH_LDG - N]);
+        lh_dslot<C>(S, sv[LH_LDG - N]);
         lh_dslots<C + 1, N - 1>(S, sv);
     }
 }
-template <int C, int N>
-__device__ __forceinline__ void lh_dissue(const lh_dldsrc &S, const unsigned (&sv)[LH_LDG][LH_LQ]) {
+template <int C, int N, class SRC>
+__device__ __forceinline__ void lh_dissue(const SRC &S, const unsigned (&sv)[LH_LDG][SRC::nq]) {
     if constexpr (N > 0 && C < LH_DCOLS) {
         S.issue(sv[LH_LDG - N], C % LH_LD);
         lh_dissue<C + 1, N - 1>(S, sv);
     }
 }
-template <int X>
-struct lh_unroll_decode_lds {
-    __device__ __forceinline__ static void run(lh_word (&v)[LH_M][8], const lh_dldsrc &S, int lo, int lo8) {
-        if constexpr (X < LH_DCOLS) {
-            constexpr int issued = (LH_LD + LH_LDG * (X / LH_LDG)) < LH_DCOLS ? (LH_LD + LH_LDG * (X / LH_LDG)) : LH_DCOLS;
-            constexpr int ahead = issued - 1 - X;
-            unsigned sv[LH_LQ];
-            if constexpr (LH_LDG == 1 && X + LH_LD < LH_DCOLS) S.slots<(X + LH_LD < LH_DCOLS ? X + LH_LD : 0)>(sv);
-            constexpr bool refill = LH_LDG > 1 && (X + 1) % LH_LDG == 0 && LH_LD + X + 1 - LH_LDG < LH_DCOLS;
-            unsigned svg[LH_LDG][LH_LQ];
-            if constexpr (refill) lh_dslots<LH_LD + X + 1 - LH_LDG, LH_LDG>(S, svg);
-            lh_wait_vmcnt<LH_LQ * ahead>();
-            asm volatile("" ::: "memory");  // no LDS read moves above the wait
-            lh_word d[8];
-            lh_slot_col(d, S.ring + (X % LH_LD) * (LH_LQ * 1024), lo, lo8);
-            lh_dcombine<X, LH_LDS_REC_FIRST>(v, d);
-            lh_dopaque(v);
-            if constexpr (LH_LDG == 1 && X + LH_LD < LH_DCOLS) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slot's reads are done
-                S.issue(sv, X % LH_LD);
-            } else if constexpr (refill) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slots' reads are done
-                lh_dissue<LH_LD + X + 1 - LH_LDG, LH_LDG>(S, svg);
-            }
-            lh_unroll_decode_lds<X + 1>::run(v, S, lo, lo8);
+// Phase A over the k + m columns; `col(d, slot)` reads the lane's 8 words of the column in `slot`.
+template <int X, class SRC, class COL>
+__device__ __forceinline__ void lh_unroll_decode_lds(lh_word (&v)[LH_M][8], const SRC &S, const COL &col) {
+    if constexpr (X < LH_DCOLS) {
+        constexpr int issued = (LH_LD + LH_LDG * (X / LH_LDG)) < LH_DCOLS ? (LH_LD + LH_LDG * (X / LH_LDG)) : LH_DCOLS;
+        constexpr int ahead = issued - 1 - X;
+        unsigned sv[SRC::nq];
+        if constexpr (LH_LDG == 1 && X + LH_LD < LH_DCOLS) lh_dslot<(X + LH_LD < LH_DCOLS ? X + LH_LD : 0)>(S, sv);
+        constexpr bool refill = LH_LDG > 1 && (X + 1) % LH_LDG == 0 && LH_LD + X + 1 - LH_LDG < LH_DCOLS;
+        unsigned svg[LH_LDG][SRC::nq];
+        if constexpr (refill) lh_dslots<LH_LD + X + 1 - LH_LDG, LH_LDG>(S, svg);
+        lh_wait_vmcnt<SRC::nq * ahead>();
+        asm volatile("" ::: "memory");  // no LDS read moves above the wait
+        lh_word d[8];
+        col(d, S.ring + (X % LH_LD) * SRC::slot_bytes);
+        lh_dcombine<X, LH_LDS_REC_FIRST>(v, d);
+        lh_dopaque(v);
+        if constexpr (LH_LDG == 1 && X + LH_LD < LH_DCOLS) {
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slot's reads are done
+            S.issue(sv, X % LH_LD);
+        } else if constexpr (refill) {
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slots' reads are done
+            lh_dissue<LH_LD + X + 1 - LH_LDG, LH_LDG>(S, svg);
         }
+        lh_unroll_decode_lds<X + 1>(v, S, col);
     }
-};
-template <int X = 0>
-__device__ __forceinline__ void lh_decode_lds_prologue(const lh_dldsrc &S) {
+}
+template <int X = 0, class SRC>
+__device__ __forceinline__ void lh_decode_lds_prologue(const SRC &S) {
     if constexpr (X < LH_LD && X < LH_DCOLS) {
-        unsigned sv[LH_LQ];
-        S.slots<X>(sv);
+        unsigned sv[SRC::nq];
+        lh_dslot<X>(S, sv);
         S.issue(sv, X);
         lh_decode_lds_prologue<X + 1>(S);
     }
-}
-// Phase B and the stores of a stripe's recovered blocks: block i = sum_r coef[i][r] V_r, stored
-// at the slot `dst(out slot i)` returns (the lane's chunk of it); the last lane of a stripe
-// funnels the previous lane's word (its chunk's last LH_VLAST bytes are its own).
-// (VL: the last lane's own bytes, sub: the sub-block size -- LH_VLAST, LH_SUB except in the
-// block-size family)
-template <int VL, class DST>
-__device__ __forceinline__ void lh_fused_out_g(const lh_word (&v)[LH_M][8], const lh_plan_regs &pr, bool last, int sub,
-                                               DST dst) {
-    const int e = pr.e;
-#pragma unroll
-    for (int i = 0; i < LH_EMAX; ++i) {
-        if (i < e) {  // stripe-uniform: the funnel's source lane is active too
-            lh_word o[8];
-#pragma unroll
-            for (int y = 0; y < 8; ++y)
-#pragma unroll
-                for (int q = 0; q < LH_NW; ++q) o[y].v[q] = 0;
-#pragma unroll
-            for (int t = 7; t >= 0; --t) {
-                if (t != 7) {
-                    lh_word t7;
-#pragma unroll
-                    for (int q = 0; q < LH_NW; ++q) t7.v[q] = lh_x3(o[0].v[q], o[1].v[q], o[2].v[q]) ^ o[7].v[q];
-#pragma unroll
-                    for (int y = 0; y < 7; ++y) o[y] = o[y + 1];
-                    o[7] = t7;
-                }
-#pragma unroll
-                for (int r = 0; r < LH_M; ++r) {
-                    const int idx = i * LH_M + r;
-                    const unsigned int mask =
-                        (unsigned int)((int)(pr.coefw[idx / 4] << (31 - (8 * (idx % 4) + t))) >> 31);
-#pragma unroll
-                    for (int y = 0; y < 8; ++y)
-#pragma unroll
-                        for (int q = 0; q < LH_NW; ++q) o[y].v[q] = lh_xand(o[y].v[q], v[r][y].v[q], mask);
-                }
-#if LH_PIN_WORDS & 2
-                lh_pin8w(o);
-#else
-                lh_pin8(o);
-#endif
-            }
-            unsigned char *d = dst((int)LH_BYTE(pr.outw, i));
-            // (Holding a block's last sub-row back to store it right before the next block's
-            // first measured slower, write bytes unchanged: profiles/r10w_store_order_k29m4.txt.)
-#pragma unroll
-            for (int y = 0; y < 8; ++y) {
-                lh_word w = o[y];
-                if constexpr (VL != 8) {
-                    const lh_word f = lh_funnel<VL>(lh_row_shr1(w.v[0]), lh_row_shr1(w.v[1]), w.v[0], w.v[1]);
-                    w.v[0] = last ? f.v[0] : w.v[0];
-                    w.v[1] = last ? f.v[1] : w.v[1];
-                }
-                lh_store(d + y * sub, w);
-                asm volatile("" ::: "memory");
-            }
-        }
-    }
-}
-template <class DST>
-__device__ __forceinline__ void lh_fused_out(const lh_word (&v)[LH_M][8], const lh_plan_regs &pr, bool last, DST dst) {
-    lh_fused_out_g<LH_VLAST>(v, pr, last, LH_SUB, dst);
 }
 // One wave's stripe group; `work`: this lane's stripe has a plan (lh_fused_plan true).
 // Every lane of the wave runs this (the DMAs need them all); only working lanes solve and store.
@@ -2011,21 +1946,36 @@ __device__ __forceinline__ void lh_fused_wave_lds(const lh_lane &l, long long wa
     const int lo = (sl < LH_SPW ? sl : LH_SPW - 1) * LH_BYTES + 8 * c;
     int lo8 = lo + 8;
     asm volatile("" : "+v"(lo8));
-    lh_unroll_decode_lds<0>::run(v, S, lo, lo8);
+    lh_unroll_decode_lds<0>(v, S, [&](lh_word (&d)[8], const unsigned char *slot) { lh_slot_col(d, slot, lo, lo8); });
     if (!work) return;
-    // Phase B as lh_dec_phase_b; the stores as the LDS encode's.  (Storing the recovered
+    // Phase B as the plain decode's; the stores as the LDS encode's.  (Storing the recovered
     // blocks through the ring as the encode does measured slower in place:
     // profiles/r5l_tune_k29m4_flat_dec.txt, 0.604 against 0.574 ms.)
 #if LH_PTR
-    lh_fused_out(v, pr, l.last, [&](int slot) {
+    lh_phase_b<LH_VLAST, true>(v, pr, l.last, LH_SUB, [&](int slot) {
         return (unsigned char *)S.pt[sl * (LH_K + 1) + slot] + (l.last ? LH_SUB - 8 : 8 * c);
     });
 #else
     unsigned char *base = blocks + l.stripe * stripe_stride + (l.last ? LH_SUB - 8 : 8 * c);
-    lh_fused_out(v, pr, l.last, [&](int slot) { return base + (long long)slot * LH_BYTES; });
+    lh_phase_b<LH_VLAST, true>(v, pr, l.last, LH_SUB, [&](int slot) { return base + (long long)slot * LH_BYTES; });
 #endif
 }
 #endif  // LH_LDS
+
+// The fused decode's LDS tables, filled by the workgroup (then a barrier): exp, log and the
+// generator (lh_fused_solve).
+__device__ __forceinline__ void lh_fused_tables(unsigned char (&gexp)[1024], short (&glog)[256],
+                                                unsigned char (&gmat)[LH_M * LH_K],
+                                                const unsigned char *__restrict__ gf_exp,
+                                                const short *__restrict__ gf_log) {
+    for (int i = threadIdx.x; i < 256; i += blockDim.x) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) gexp[i + 256 * q] = gf_exp[(i + 256 * q) % 255];
+        glog[i] = gf_log[i];
+    }
+    for (int i = threadIdx.x; i < LH_M * LH_K; i += blockDim.x) gmat[i] = LH_GRAW[i / LH_K][i % LH_K];
+    __syncthreads();
+}
 
 #ifndef LH_DEC_LB
 #define LH_DEC_LB 1  // min waves per SIMD the register allocator must allow (tools/tune.py)
@@ -2040,13 +1990,7 @@ __device__ __forceinline__ void lh_fused_body(unsigned char *__restrict__ blocks
     __shared__ short glog[256];
     __shared__ unsigned char gmat[LH_M * LH_K];
     __shared__ __attribute__((aligned(16))) unsigned char scratch[LH_DWPB][LH_SPW > 0 ? LH_SPW : 1][LH_SR];
-    for (int i = threadIdx.x; i < 256; i += blockDim.x) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) gexp[i + 256 * q] = gf_exp[(i + 256 * q) % 255];
-        glog[i] = gf_log[i];
-    }
-    for (int i = threadIdx.x; i < LH_M * LH_K; i += blockDim.x) gmat[i] = LH_GRAW[i / LH_K][i % LH_K];
-    __syncthreads();
+    lh_fused_tables(gexp, glog, gmat, gf_exp, gf_log);
     const int wid = threadIdx.x >> 6;
     LH_WAVE_LOOP(stripes) {
         const lh_lane l = lh_map_lane(stripes, lh_w);
@@ -2092,28 +2036,18 @@ lh_jit_decode_fused(unsigned char *__restrict__ blocks, long long stripe_stride,
 #define LH_FNRW 8                                   // Block.row bytes per lane, at most
 #define LH_FSPW (64 / ((LH_K + LH_FNRW - 1) / LH_FNRW))  // stripes per wave, at most
 #define LH_FRS (4 * 1024 + 16)                      // ring slot: 4 KiB (+16: the last lane's second word)
-struct lh_grt {
-    int nch, nrw;
+struct lh_grt {  // (wave-uniform; filled once per launch)
+    int bytes, sub, nch, spw, cch, nrw;  // cch: 16-byte chunks per block
     unsigned long long lanes;
     static constexpr int maxrw = LH_FNRW;
 };
-struct lh_dfam {
-    int bytes, sub, nch, spw, cch;
-};
 struct lh_fdsrc {
+    static constexpr int nq = 4, slot_bytes = LH_FRS;
     __amdgpu_buffer_rsrc_t rs;
     int joff[4], jsc[4];  // DMA chunk q: byte offset in the wave's stripes (block 0); its stripe's scratch offset or < 0
     int bytes;
     const unsigned char *scr;
     unsigned char *ring;
-    template <int X>
-    __device__ __forceinline__ void slots(unsigned (&sv)[4]) const {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const unsigned b = scr[(jsc[q] & 0x7FFFFFFF) + lh_dmoff<X>::v];
-            sv[q] = jsc[q] < 0 ? 0xFFu : b;
-        }
-    }
     __device__ __forceinline__ void issue(const unsigned (&sv)[4], int slot) const {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -2127,20 +2061,6 @@ struct lh_fdsrc {
         }
     }
 };
-template <int C, int N>
-__device__ __forceinline__ void lh_fdslots(const lh_fdsrc &S, unsigned (&sv)[LH_LDG][4]) {
-    if constexpr (N > 0 && C < LH_DCOLS) {
-        S.slots<C>(sv[LH_LDG - N]);
-        lh_fdslots<C + 1, N - 1>(S, sv);
-    }
-}
-template <int C, int N>
-__device__ __forceinline__ void lh_fdissue(const lh_fdsrc &S, const unsigned (&sv)[LH_LDG][4]) {
-    if constexpr (N > 0 && C < LH_DCOLS) {
-        S.issue(sv[LH_LDG - N], C % LH_LD);
-        lh_fdissue<C + 1, N - 1>(S, sv);
-    }
-}
 // A column's words, each read next to its use (the compiler's schedule; the encode's family
 // issues all 16 reads first, lh_fam_col).
 template <int R>
@@ -2160,70 +2080,32 @@ __device__ __forceinline__ void lh_dfam_col(lh_word (&d)[8], const unsigned char
         }
     }
 }
-// Phase A over the k + m columns, as lh_unroll_decode_lds (refills of LH_LDG slots).
-template <int X, int R>
-struct lh_unroll_dfam {
-    __device__ __forceinline__ static void run(lh_word (&v)[LH_M][8], const lh_fdsrc &S, const int (&ad)[8]) {
-        if constexpr (X < LH_DCOLS) {
-            constexpr int issued = (LH_LD + LH_LDG * (X / LH_LDG)) < LH_DCOLS ? (LH_LD + LH_LDG * (X / LH_LDG)) : LH_DCOLS;
-            constexpr int ahead = issued - 1 - X;
-            unsigned sv[4];
-            if constexpr (LH_LDG == 1 && X + LH_LD < LH_DCOLS) S.slots<(X + LH_LD < LH_DCOLS ? X + LH_LD : 0)>(sv);
-            constexpr bool refill = LH_LDG > 1 && (X + 1) % LH_LDG == 0 && LH_LD + X + 1 - LH_LDG < LH_DCOLS;
-            unsigned svg[LH_LDG][4];
-            if constexpr (refill) lh_fdslots<LH_LD + X + 1 - LH_LDG, LH_LDG>(S, svg);
-            lh_wait_vmcnt<4 * ahead>();
-            asm volatile("" ::: "memory");  // no LDS read moves above the wait
-            lh_word d[8];
-            lh_dfam_col<R>(d, S.ring + (X % LH_LD) * LH_FRS, ad);
-            lh_dcombine<X, LH_LDS_REC_FIRST>(v, d);
-            lh_dopaque(v);
-            if constexpr (LH_LDG == 1 && X + LH_LD < LH_DCOLS) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slot's reads are done
-                S.issue(sv, X % LH_LD);
-            } else if constexpr (refill) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slots' reads are done
-                lh_fdissue<LH_LD + X + 1 - LH_LDG, LH_LDG>(S, svg);
-            }
-            lh_unroll_dfam<X + 1, R>::run(v, S, ad);
-        }
-    }
-};
-template <int X = 0>
-__device__ __forceinline__ void lh_dfam_prologue(const lh_fdsrc &S) {
-    if constexpr (X < LH_LD && X < LH_DCOLS) {
-        unsigned sv[4];
-        S.slots<X>(sv);
-        S.issue(sv, X);
-        lh_dfam_prologue<X + 1>(S);
-    }
-}
 template <int R>
-__device__ __forceinline__ void lh_fused_wave_fam(const lh_dfam &F, const lh_lane &l, long long wave, int c, int sl, bool work,
+__device__ __forceinline__ void lh_fused_wave_fam(const lh_grt &g, const lh_lane &l, long long wave, int c, int sl, bool work,
                                                   const unsigned char *scr, unsigned char *__restrict__ blocks,
                                                   long long stripe_stride, int stripes, const lh_fused_solve &sv,
                                                   lh_plan_regs &pr, unsigned char *ring) {
     const int lane = threadIdx.x & 63;
-    const long long s0 = (long long)__builtin_amdgcn_readfirstlane((int)wave) * F.spw;  // wave-uniform
+    const long long s0 = (long long)__builtin_amdgcn_readfirstlane((int)wave) * g.spw;  // wave-uniform
     if (s0 >= stripes) return;  // wave-uniform
-    const int nst = (int)((stripes - s0) < F.spw ? (stripes - s0) : F.spw);
+    const int nst = (int)((stripes - s0) < g.spw ? (stripes - s0) : g.spw);
     const unsigned long long wm = __ballot(work);
     if (wm == 0) return;  // wave-uniform
     lh_fdsrc S;
     S.rs = __builtin_amdgcn_make_buffer_rsrc(blocks + s0 * stripe_stride, 0, (int)(nst * stripe_stride), 0x00020000);
-    S.bytes = F.bytes;
+    S.bytes = g.bytes;
     S.scr = scr;
     S.ring = ring;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {  // chunk j = 64 q + lane of the image [stripe][bytes]
         const int j = 64 * q + lane;
-        const int js = j / F.cch;
-        const bool on = js < nst && ((wm >> (js * F.nch)) & 1ull);
-        S.joff[q] = js * (int)stripe_stride + (j - js * F.cch) * 16;
+        const int js = j / g.cch;
+        const bool on = js < nst && ((wm >> (js * g.nch)) & 1ull);
+        S.joff[q] = js * (int)stripe_stride + (j - js * g.cch) * 16;
         S.jsc[q] = on ? js * LH_SR : (int)0x80000000;
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the previous group's ring reads are done
-    lh_dfam_prologue(S);
+    lh_decode_lds_prologue(S);
     if (work) sv(pr);  // the solve, while the first columns land
     lh_word v[LH_M][8];
 #pragma unroll
@@ -2232,30 +2114,30 @@ __device__ __forceinline__ void lh_fused_wave_fam(const lh_dfam &F, const lh_lan
         for (int y = 0; y < 8; ++y)
 #pragma unroll
             for (int i = 0; i < LH_NW; ++i) v[r][y].v[i] = 0;
-    const int lo = (sl < F.spw ? sl : F.spw - 1) * F.bytes + 8 * c;
+    const int lo = (sl < g.spw ? sl : g.spw - 1) * g.bytes + 8 * c;
     int ad[8];
 #pragma unroll
-    for (int b = 0; b < 8; ++b) ad[b] = lo + b * (F.sub - R);
-    lh_unroll_dfam<0, R>::run(v, S, ad);
+    for (int b = 0; b < 8; ++b) ad[b] = lo + b * (g.sub - R);
+    lh_unroll_decode_lds<0>(v, S, [&](lh_word (&d)[8], const unsigned char *slot) { lh_dfam_col<R>(d, slot, ad); });
     if (!work) return;
-    unsigned char *base = blocks + l.stripe * stripe_stride + (l.last ? F.sub - 8 : 8 * c);
-    lh_fused_out_g<R == 0 ? 8 : R>(v, pr, l.last, F.sub, [&](int slot) { return base + (long long)slot * F.bytes; });
+    unsigned char *base = blocks + l.stripe * stripe_stride + (l.last ? g.sub - 8 : 8 * c);
+    lh_phase_b<R == 0 ? 8 : R, true>(v, pr, l.last, g.sub, [&](int slot) { return base + (long long)slot * g.bytes; });
 }
 template <int R>
-__device__ __forceinline__ void lh_dfam_body(const lh_dfam &F, const lh_grt &g, unsigned char *__restrict__ blocks,
+__device__ __forceinline__ void lh_dfam_body(const lh_grt &g, unsigned char *__restrict__ blocks,
                                              long long stripe_stride, unsigned char *__restrict__ rows,
                                              signed char *__restrict__ status, const unsigned char *gexp, const short *glog,
                                              const unsigned char *gmat, unsigned char (*scratch)[LH_FSPW][LH_SR],
                                              unsigned char *ring, int stripes) {
     const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int sl = lane / F.nch, c = lane - sl * F.nch;
-    const long long nw = ((long long)stripes + F.spw - 1) / F.spw;
+    const int sl = lane / g.nch, c = lane - sl * g.nch;
+    const long long nw = ((long long)stripes + g.spw - 1) / g.spw;
     const long long ws = (long long)gridDim.x * (blockDim.x >> 6);
     for (long long w = (lh_block_id() * blockDim.x + threadIdx.x) >> 6; w < nw; w += ws) {
         lh_lane l;
-        l.stripe = w * F.spw + sl;
-        l.active = sl < F.spw && l.stripe < stripes;
-        l.last = c == F.nch - 1;
+        l.stripe = w * g.spw + sl;
+        l.active = sl < g.spw && l.stripe < stripes;
+        l.last = c == g.nch - 1;
         l.p = 0;  // (unused here)
         lh_plan_regs pr;
         lh_fused_solve sv;
@@ -2265,7 +2147,7 @@ __device__ __forceinline__ void lh_dfam_body(const lh_dfam &F, const lh_grt &g, 
         unsigned int rowv[LH_FNRW];
         lh_fused_rows(g, l, c, rows, rowv);
         const bool work = l.active && lh_fused_plan(g, l, c, sl, &scratch[wid][sl][0], rowv, rows, status, sv, pr);
-        lh_fused_wave_fam<R>(F, l, w, c, sl, work, &scratch[wid][0][0], blocks, stripe_stride, stripes, sv, pr, ring);
+        lh_fused_wave_fam<R>(g, l, w, c, sl, work, &scratch[wid][0][0], blocks, stripe_stride, stripes, sv, pr, ring);
     }
 }
 extern "C" __global__ void __launch_bounds__(256, LH_DEC_LB)
@@ -2278,31 +2160,23 @@ lh_jit_decode_fused(unsigned char *__restrict__ blocks, long long stripe_stride,
     __shared__ unsigned char gmat[LH_M * LH_K];
     __shared__ __attribute__((aligned(16))) unsigned char scratch[4][LH_FSPW][LH_SR];
     __shared__ __attribute__((aligned(16))) unsigned char lh_fdring[4][LH_LD * LH_FRS];
-    for (int i = threadIdx.x; i < 256; i += blockDim.x) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) gexp[i + 256 * q] = gf_exp[(i + 256 * q) % 255];
-        glog[i] = gf_log[i];
-    }
-    for (int i = threadIdx.x; i < LH_M * LH_K; i += blockDim.x) gmat[i] = LH_GRAW[i / LH_K][i % LH_K];
-    __syncthreads();
-    lh_dfam F;
-    F.bytes = bytes;
-    F.sub = bytes >> 3;
-    F.nch = (F.sub + 7) >> 3;
-    F.spw = 64 / F.nch;
-    F.cch = bytes >> 4;
+    lh_fused_tables(gexp, glog, gmat, gf_exp, gf_log);
     lh_grt g;
-    g.nch = F.nch;
-    g.nrw = (LH_K + F.nch - 1) / F.nch;
-    g.lanes = F.nch >= 64 ? ~0ull : ((1ull << F.nch) - 1);
+    g.bytes = bytes;
+    g.sub = bytes >> 3;
+    g.nch = (g.sub + 7) >> 3;
+    g.spw = 64 / g.nch;
+    g.cch = bytes >> 4;
+    g.nrw = (LH_K + g.nch - 1) / g.nch;
+    g.lanes = g.nch >= 64 ? ~0ull : ((1ull << g.nch) - 1);
     // (the wave index made wave-uniform explicitly: the ring's LDS addresses, the DMAs' M0, then
     // live in SGPRs, not in 16 VGPRs read back with readfirstlane before every DMA)
     unsigned char *ring = lh_fdring[__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))];
-    switch (F.sub & 7) {  // (launch-uniform; bytes % 16 == 0 makes sub even)
-        case 0: lh_dfam_body<0>(F, g, blocks, stripe_stride, rows, status, gexp, glog, gmat, scratch, ring, stripes); break;
-        case 2: lh_dfam_body<2>(F, g, blocks, stripe_stride, rows, status, gexp, glog, gmat, scratch, ring, stripes); break;
-        case 4: lh_dfam_body<4>(F, g, blocks, stripe_stride, rows, status, gexp, glog, gmat, scratch, ring, stripes); break;
-        default: lh_dfam_body<6>(F, g, blocks, stripe_stride, rows, status, gexp, glog, gmat, scratch, ring, stripes); break;
+    switch (g.sub & 7) {  // (launch-uniform; bytes % 16 == 0 makes sub even)
+        case 0: lh_dfam_body<0>(g, blocks, stripe_stride, rows, status, gexp, glog, gmat, scratch, ring, stripes); break;
+        case 2: lh_dfam_body<2>(g, blocks, stripe_stride, rows, status, gexp, glog, gmat, scratch, ring, stripes); break;
+        case 4: lh_dfam_body<4>(g, blocks, stripe_stride, rows, status, gexp, glog, gmat, scratch, ring, stripes); break;
+        default: lh_dfam_body<6>(g, blocks, stripe_stride, rows, status, gexp, glog, gmat, scratch, ring, stripes); break;
     }
 }
 #endif  // LH_FAMILY && LH_ROLE == 2

@@ -15,6 +15,21 @@ import tempfile
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
+NOTE_KEYS = ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count",
+             "group_segment_fixed_size")
+
+
+def kernel_notes(co):
+    """{kernel name: {note key: value}} of a code object's amdhsa.kernels metadata (-1: absent)."""
+    notes = subprocess.run([READELF, "--notes", co], capture_output=True, text=True).stdout
+    out = {}
+    for blk in re.split(r"\n\s+- \.", notes)[1:]:  # one amdhsa.kernels entry each
+        mm = re.search(r"\.name:\s+(\S+)", blk)
+        if not mm or mm.group(1).endswith(".kd") or "vgpr_count" not in blk:
+            continue
+        vals = {key: re.search(r"\." + key + r":\s+(\d+)", blk) for key in NOTE_KEYS}
+        out[mm.group(1)] = {key: int(v.group(1)) if v else -1 for key, v in vals.items()}
+    return out
 
 
 def main():
@@ -30,18 +45,10 @@ def main():
         rc = lh.lib().cauchy_256_jit_precompile(k, m, nbytes)
         assert rc == 0, (rc, lh.last_error())
         for co in sorted(glob.glob(os.path.join(tmp, "**", "*.co"), recursive=True)):
-            notes = subprocess.run([READELF, "--notes", co], capture_output=True, text=True).stdout
-            for blk in re.split(r"\n\s+- \.", notes)[1:]:  # one amdhsa.kernels entry each
-                mm = re.search(r"\.name:\s+(\S+)", blk)
-                if not mm or mm.group(1).endswith(".kd") or "vgpr_count" not in blk:
-                    continue
-                name = mm.group(1)
-                def f(key):
-                    mm = re.search(r"\." + key + r":\s+(\d+)", blk)
-                    return int(mm.group(1)) if mm else -1
-                print(f"{name:28s} vgpr {f('vgpr_count'):4d} agpr {f('agpr_count'):3d} sgpr {f('sgpr_count'):3d} "
-                      f"spill v/s {f('vgpr_spill_count')}/{f('sgpr_spill_count')} "
-                      f"lds {f('group_segment_fixed_size'):6d}  ({os.path.getsize(co)} B object)")
+            for name, f in kernel_notes(co).items():
+                print(f"{name:28s} vgpr {f['vgpr_count']:4d} agpr {f['agpr_count']:3d} sgpr {f['sgpr_count']:3d} "
+                      f"spill v/s {f['vgpr_spill_count']}/{f['sgpr_spill_count']} "
+                      f"lds {f['group_segment_fixed_size']:6d}  ({os.path.getsize(co)} B object)")
 
 
 if __name__ == "__main__":
