@@ -107,7 +107,12 @@ const char *cauchy_256_last_launch(void);
  * (k, m) for every 16-byte-multiple size up to 4 KiB with m <= 6) can serve the encode: batch
  * and drop-in encodes take it while no size-specialised module is loaded or cached.  `what` =
  * 9: the same for the decode's family (the fused decode: min(k, m) <= 4, k <= 64, at least
- * ceil(k / 8) 8-byte lanes per stripe). */
+ * ceil(k / 8) 8-byte lanes per stripe).  `what` = 10 (encode) / 11 (decode): the number of
+ * stripes one workgroup of the shape's strided specialised kernel covers (the stripes of a
+ * wave times the waves of a workgroup, as the launches size their grids; the family form under
+ * the LH_FAMILY=1 define); 1 when a stripe fills a wave or more (the windowed kernels
+ * included), 0 when no specialised configuration serves the shape.  Like 2 / 5 / 8 / 9 it reads
+ * the configuration only and needs no device. */
 int cauchy_256_batch_path(int k, int m, int block_bytes, int what);
 
 /* Compile the specialised kernels of a shape into the on-disk code-object cache

@@ -325,6 +325,14 @@ def lds_staged(k, m, block_bytes, decode=False):
     return lib().cauchy_256_batch_path(k, m, block_bytes, 5 if decode else 2) == 1
 
 
+def stripes_per_workgroup(k, m, block_bytes, decode=False):
+    """Stripes one workgroup of the shape's strided specialised encode (decode) kernel covers
+    (cauchy_256_batch_path what = 10 / 11; codec.cpp jit_encode_blocks / jit_blocks): 1 when a
+    stripe fills a wave or more, 0 when no specialised configuration serves the shape.  Needs no
+    device."""
+    return lib().cauchy_256_batch_path(k, m, block_bytes, 11 if decode else 10)
+
+
 def jump_lanes(k, m, block_bytes, decode=False):
     """Dword lanes per sub-block of the generic jump kernel the library launches for this
     shape on the current device (codec.cpp jump_layout): 1 = lh_apply_jump_kernel, 2 =

@@ -1613,8 +1613,17 @@ LH_API int cauchy_256_batch_path(int k, int m, int block_bytes, int what) {
             return a.dw;
         }
         std::vector<lh::JitConfig> cfgs;  // the strided module of the role: none, windowed or register network
-        lh::shape_configs(k, m, block_bytes, what == 1, lh::kFormStrided, &cfgs);
+        lh::shape_configs(k, m, block_bytes, what == 1 || what == 11, lh::kFormStrided, &cfgs);
         if (cfgs.empty()) return 0;
+        if (what == 10 || what == 11) {
+            // Stripes per workgroup of the strided specialised kernel: the stripes of a wave times
+            // the waves of a workgroup, as jit_encode_blocks (launch_jit_encode, its family form
+            // included: jit_family_config_for sets the same spw) and jit_blocks (launch_jit_decode,
+            // launch_jit_decode_fused) size their grids; 1 when a stripe fills a wave or more (the
+            // windowed kernels included).
+            const lh::JitConfig &c = cfgs[0];
+            return c.spw ? c.spw * (what == 10 ? c.enc_wpb : 4) : 1;
+        }
         if (cfgs[0].win) return what == 0 ? 3 : 4;
         // Decode: 2 when the plan is computed inside the specialised kernel (jit_codec.hip,
         // LH_FUSED; jit.cpp: cfg.plain = 0).
@@ -1626,6 +1635,7 @@ LH_API int cauchy_256_frame_batch(int k, int m, int block_bytes, int stripes, co
                                   long long data_stride, const void *d_recovery, long long recovery_stride,
                                   void *d_packets, long long packet_stride, void *stream) {
     LH_TRY
+        lh::LaunchTrace trace;
         if (k < 1 || m < 0 || k + m > 256 || block_bytes <= 0 || stripes < 0 ||
             data_stride < (long long)k * block_bytes || (m > 0 && recovery_stride < (long long)m * block_bytes) ||
             packet_stride < (long long)(k + m) * (block_bytes + 1))
@@ -1655,6 +1665,7 @@ LH_API int cauchy_256_unframe_batch(int k, int block_bytes, int stripes, const v
                                     long long packet_stride, void *d_blocks, long long stripe_stride,
                                     unsigned char *d_rows, void *stream) {
     LH_TRY
+        lh::LaunchTrace trace;
         if (k < 1 || k > 256 || block_bytes <= 0 || stripes < 0 || packet_stride < (long long)k * (block_bytes + 1) ||
             stripe_stride < (long long)k * block_bytes)
             return lh::fail(lh::kInvalid, "invalid framing parameters");

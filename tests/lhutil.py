@@ -260,6 +260,29 @@ def pattern_digest(rcs, rows_out, blocks_out):
                                np.asarray(blocks_out, dtype=np.uint8).reshape(-1)]))
 
 
+# ------------------------------------------------------------------ batch sizes
+# tests/test_gpu_stripe_counts.py runs every prefix length of one prepared batch that meets an
+# edge of a kernel's stripe-to-workgroup mapping (tests/test_lhutil_counts.py holds the set).
+COUNT_GRIDS = (7, 8, 9, 15, 16, 17)   # workgroups around the XCD renumbering's 8 and 16
+
+
+def stripe_counts(tile, extra=(), grids=COUNT_GRIDS):
+    """The batch sizes to sweep for a kernel whose workgroup covers `tile` stripes (>= 1),
+    ascending and unique: every n in 1 .. 2 tile + 1 (each partial-wave and partial-workgroup
+    residue, twice), g tile - 1, g tile, g tile + 1 for g in `grids` (a grid just below, at and
+    past 8 and 16 workgroups), and `extra`.  The largest is the batch to prepare."""
+    tile = int(tile)
+    if tile < 1:
+        raise ValueError("a workgroup covers at least one stripe")
+    counts = set(range(1, 2 * tile + 2))
+    for g in grids:
+        counts.update((g * tile - 1, g * tile, g * tile + 1))
+    counts.update(int(n) for n in extra)
+    if min(counts) < 1:
+        raise ValueError("batch sizes start at 1")
+    return sorted(counts)
+
+
 # ------------------------------------------------------------------ invalid stripes
 # include/cauchy_256_batch.h: a stripe whose rows hold a duplicate or a row >= k + m is
 # invalid (status -1, left untouched).  `invalidate_rows` breaks a valid stripe in one named

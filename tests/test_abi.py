@@ -86,7 +86,8 @@ def test_specialisation_policy():
 
 # (k, m, bytes, what, code): cauchy_256_batch_path on both sides of each boundary of the batch
 # routes, recorded from the library before codec.cpp's routes were collapsed into one function
-# (what 0 / 1: encode / decode path, 2 / 5: LDS staging, 8 / 9: block-size family).
+# (what 0 / 1: encode / decode path, 2 / 5: LDS staging, 8 / 9: block-size family; 10 / 11, added
+# later: the stripes per workgroup of the specialised encode / decode, test_stripes_per_workgroup).
 CLASSIFICATION = [
     (29, 4, 1296, 0, 1), (29, 4, 1296, 1, 2), (29, 8, 1296, 1, 1),
     (64, 4, 1296, 1, 2), (65, 4, 1296, 1, 1),          # fused plan: k <= 64
@@ -114,6 +115,37 @@ def test_classification_table():
     path = longhair_amd.lib().cauchy_256_batch_path
     got = [(k, m, b, what, path(k, m, b, what)) for k, m, b, what, _ in CLASSIFICATION]
     assert got == CLASSIFICATION
+
+
+def test_stripes_per_workgroup(monkeypatch):
+    """cauchy_256_batch_path what = 10 / 11: the stripes one workgroup of the strided specialised
+    encode / decode covers (stripes per wave x waves per workgroup, codec.cpp jit_encode_blocks /
+    jit_blocks), from the configuration alone -- tests/test_gpu_stripe_counts.py sizes its sweeps
+    by it."""
+    import longhair_amd
+    path = longhair_amd.lib().cauchy_256_batch_path
+    spw = longhair_amd.stripes_per_workgroup
+    assert [path(10, 4, 64, w) for w in (10, 11)] == [256, 256]        # one lane per stripe: 64 x 4 waves
+    assert [path(29, 4, 1296, w) for w in (10, 11)] == [12, 12]        # nch 21: 3 stripes per wave
+    assert [path(8, 4, 4096, w) for w in (10, 11)] == [4, 4]           # nch 64: one stripe per wave
+    assert path(64, 4, 4096, 11) == 4
+    # m = 3 at 8128 bytes: the encode's 16-byte lanes fill one wave (nch 64), the decode's 8-byte
+    # lanes (a fourth accumulator row) take two waves per stripe (nch 127)
+    assert [path(8, 3, 8128, w) for w in (10, 11)] == [4, 1]
+    assert [path(40, 13, 2048, 10), path(40, 12, 2048, 11)] == [1, 1]  # the windowed kernels
+    assert path(65, 4, 64, 11) == 256 and path(10, 5, 64, 11) == 256   # lh_jit_decode after the planner
+    assert path(65, 4, 1296, 11) == 12
+    # no specialised configuration: 0
+    assert [path(9, 9, 64, 11), path(10, 13, 64, 10), path(129, 4, 1296, 10), path(29, 4, 1300, 11)] == [0, 0, 0, 0]
+    assert path(10, 1, 100, 10) == 0 and path(1, 3, 40, 11) == 0
+    assert spw(29, 4, 1296) == 12 and spw(29, 4, 1296, decode=True) == 12 and spw(9, 9, 64, True) == 0
+    # the block-size family's kernels under the define the tests force them with
+    monkeypatch.setenv("LONGHAIR_AMD_JIT_DEFINES", "LH_FAMILY=1")
+    assert [path(29, 4, 1312, w) for w in (10, 11)] == [12, 12]        # 8-byte lanes, nch 21
+    assert path(4, 5, 96, 11) == 128                                   # nch 2: 32 stripes per wave
+    monkeypatch.delenv("LONGHAIR_AMD_JIT_DEFINES")
+    monkeypatch.setenv("LONGHAIR_AMD_PATH", "generic")
+    assert [path(10, 4, 64, w) for w in (10, 11)] == [0, 0]
 
 
 def test_lds_staging_policy():

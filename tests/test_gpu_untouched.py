@@ -104,7 +104,7 @@ def pick_invalid(stripes, seed, mode="quarter"):
     stripes, and seeded-random others up to about a quarter of the batch."""
     if mode == "all":
         return list(range(stripes))
-    if mode == "none":
+    if mode in ("none", "valid"):
         return []
     assert stripes >= 5, "a mixed batch needs room for four invalid stripes and a valid one"
     rng = np.random.Generator(np.random.PCG64(seed ^ 0x1234))
@@ -121,7 +121,8 @@ def mixed_case(oracle, k, m, nbytes, stripes, seed, mode="quarter"):
     """One batch's input and expected output: (blocks, rows, invalid mask, expected blocks,
     expected rows), the expectation computed once (the oracle on valid stripes only).
     mode 'quarter': a mixed batch; 'all': every stripe invalid; 'none': every stripe valid
-    with e = 0 (nothing to recover, so nothing may change)."""
+    with e = 0 (nothing to recover, so nothing may change); 'valid': every stripe valid with
+    the mixed batch's random e (m = 1, which accepts any rows, has no invalid stripe)."""
     data, rec = _encoded(oracle, k, m, nbytes, stripes, seed)
     bad = pick_invalid(stripes, seed, mode)
     if mode == "none":

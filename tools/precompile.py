@@ -35,6 +35,10 @@ KNOB_JOBS = [((29, 4, 1296), {"LONGHAIR_AMD_JIT_DEFINES": "LH_LDS=0,LH_PF=2,LH_N
 # are sweep, boundary, family and pointer-table shapes; it runs with LONGHAIR_AMD_JIT_COMPILE=0.)
 PATTERN_JOBS = [((4, 4, 8), {"LONGHAIR_AMD_NO_FUSED_PLAN": "1"})]
 
+# Modules of the batch-size sweeps (tests/test_gpu_stripe_counts.py) that no list above holds:
+# k = 65 / m = 4 at one lane per stripe, the small planner's case (its decode module only).
+STRIPE_COUNT_JOBS = [((65, 4, 64), "dec")]
+
 
 def lds_sample(n, seed=606):
     """A seeded sample of n shapes served by the LDS-staged register networks:
@@ -136,6 +140,7 @@ def main():
             jobs_list += [(sh, None) for sh in sorted(tb.JIT_SAMPLE, key=lambda s: -s[0] * s[1]) if sh not in have]
             # the erasure-pattern batches' knob module (test_gpu_patterns.py), beside the shape's own
             jobs_list += [(s, ("dec", env)) for s, env in PATTERN_JOBS]
+            jobs_list += [(s, part) for s, part in STRIPE_COUNT_JOBS]
             # the encode and decode modules of a shape in separate processes
             split = []
             for sh, part in jobs_list:
