@@ -7,7 +7,8 @@ Python view of the C-ABI library `liblonghair_amd.so` (built from longhair_amd/c
   `cauchy_256_init()`, `cauchy_256_encode(k, m, data_ptrs, recovery_blocks, block_bytes)`,
   `cauchy_256_decode(k, m, blocks, block_bytes)` and the `Block` structure, taking the same
   arguments as the C functions (ctypes pointers / arrays) and returning the same codes;
-* batched device-resident helpers on torch uint8 tensors: `encode_batch`, `decode_batch`.
+* batched device-resident helpers on torch uint8 tensors: `encode_batch`, `decode_batch`, and
+  `update_batch`, which patches the recovery blocks after a few data blocks changed.
 
 There is no CPU implementation: importing works without a GPU, but every codec call
 goes through the HIP library and fails loudly (LonghairError / non-zero codes) when no
@@ -187,6 +188,71 @@ def decode_batch_ptrs(k, m, block_bytes, block_ptrs, rows, status=None, stream=N
                                             ctypes.c_void_p(_stream_handle(stream)))
     if rc != 0:
         raise LonghairError(rc, "cauchy_256_decode_batch_ptrs")
+    return status
+
+
+def update_batch(k, recovery, cols, old, new=None, status=None, stream=None):
+    """Patch the recovery blocks of encoded stripes after data blocks changed
+    (cauchy_256_update_batch): recovery becomes what encode_batch would write for the patched data.
+
+    recovery: uint8 CUDA tensor [stripes, m, block_bytes], patched in place;
+    cols:     uint8 CUDA tensor [stripes, c] -- the data index of each changed block, 0xFF = no
+              change in this entry; a column may repeat (its deltas accumulate);
+    old, new: uint8 CUDA tensors [stripes, c, block_bytes], the blocks before and after; with
+              new=None `old` holds the deltas (old ^ new) themselves.
+    Returns `status` (int8 [stripes], 0 ok / -1 a column in [k, 0xFE]: that stripe is untouched)."""
+    import torch
+    _block_tensor(recovery, "recovery")
+    stripes, m, nbytes = recovery.shape
+    _cuda_tensor(cols, torch.uint8, "cols", None, True, recovery.device)
+    _require(cols.dim() == 2 and cols.shape[0] == stripes, f"cols must be [{stripes}, changes]")
+    changes = cols.shape[1]
+    _block_tensor(old, "old")
+    _require(tuple(old.shape) == (stripes, changes, nbytes), f"old must be [{stripes}, {changes}, {nbytes}]")
+    _require(old.device == recovery.device, "old must be on recovery's device")
+    if new is not None:
+        _block_tensor(new, "new")
+        _require(tuple(new.shape) == (stripes, changes, nbytes), f"new must be [{stripes}, {changes}, {nbytes}]")
+        _require(new.device == recovery.device, "new must be on recovery's device")
+    if status is None:
+        status = torch.empty((stripes,), dtype=torch.int8, device=recovery.device)
+    _cuda_tensor(status, torch.int8, "status", (stripes,), True, recovery.device)
+    rc = lib().cauchy_256_update_batch(k, m, nbytes, stripes, changes, ctypes.c_void_p(cols.data_ptr()),
+                                       ctypes.c_void_p(old.data_ptr()), ctypes.c_longlong(old.stride(0)),
+                                       ctypes.c_void_p(new.data_ptr()) if new is not None else None,
+                                       ctypes.c_longlong(new.stride(0) if new is not None else 0),
+                                       ctypes.c_void_p(recovery.data_ptr()), ctypes.c_longlong(recovery.stride(0)),
+                                       ctypes.c_void_p(status.data_ptr()), ctypes.c_void_p(_stream_handle(stream)))
+    if rc != 0:
+        raise LonghairError(rc, "cauchy_256_update_batch")
+    return status
+
+
+def update_batch_ptrs(k, m, block_bytes, cols, old_ptrs, new_ptrs, recovery_ptrs, status=None, stream=None):
+    """update_batch for blocks that sit anywhere in device memory (cauchy_256_update_batch_ptrs).
+
+    cols:          uint8 CUDA tensor [stripes, c];
+    old_ptrs:      int64 CUDA tensor [stripes, c] of device addresses (entries of 0xFF columns are
+                   not read); new_ptrs likewise, or None: old_ptrs point at the deltas;
+    recovery_ptrs: int64 CUDA tensor [stripes, m].
+    Returns `status` (int8 [stripes])."""
+    import torch
+    _cuda_tensor(cols, torch.uint8, "cols", None, True)
+    _require(cols.dim() == 2, "cols must be [stripes, changes]")
+    stripes, changes = cols.shape
+    old_t = _ptr_table(old_ptrs, stripes, changes, "old_ptrs")
+    new_t = _ptr_table(new_ptrs, stripes, changes, "new_ptrs") if new_ptrs is not None else None
+    rec_t = _ptr_table(recovery_ptrs, stripes, m, "recovery_ptrs")
+    for t, name in ((old_ptrs, "old_ptrs"), (new_ptrs, "new_ptrs"), (recovery_ptrs, "recovery_ptrs")):
+        _require(t is None or t.device == cols.device, f"{name} must be on cols' device")
+    if status is None:
+        status = torch.empty((stripes,), dtype=torch.int8, device=cols.device)
+    _cuda_tensor(status, torch.int8, "status", (stripes,), True, cols.device)
+    rc = lib().cauchy_256_update_batch_ptrs(k, m, block_bytes, stripes, changes, ctypes.c_void_p(cols.data_ptr()),
+                                            old_t, new_t, rec_t, ctypes.c_void_p(status.data_ptr()),
+                                            ctypes.c_void_p(_stream_handle(stream)))
+    if rc != 0:
+        raise LonghairError(rc, "cauchy_256_update_batch_ptrs")
     return status
 
 

@@ -61,12 +61,22 @@ EXPORTS = {
 OPTIONAL_EXPORTS = {
     "cauchy_256_debug_throw_next": (None, []),
 }
+# Every symbol include/cauchy_256_update.h declares (the recovery patch), in both libraries.
+UPDATE_EXPORTS = {
+    "cauchy_256_update_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
+                                               ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
+                                               ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p]),
+    "cauchy_256_update_batch_ptrs": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                    ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+}
 
 
 def bind(l):
-    """Set the ctypes signatures of a loaded copy of the library (every EXPORTS symbol must
-    exist; OPTIONAL_EXPORTS where present)."""
-    for name, (res, args) in EXPORTS.items():
+    """Set the ctypes signatures of a loaded copy of the library (every EXPORTS and
+    UPDATE_EXPORTS symbol must exist; OPTIONAL_EXPORTS where present)."""
+    for name, (res, args) in list(EXPORTS.items()) + list(UPDATE_EXPORTS.items()):
         f = getattr(l, name)
         f.restype = res
         f.argtypes = args

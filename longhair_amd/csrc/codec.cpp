@@ -1,5 +1,5 @@
 // codec.cpp -- the C ABI: drop-in cauchy_256.h entry points and the batched
-// device-resident extension (cauchy_256_batch.h).
+// device-resident extension (cauchy_256_batch.h, cauchy_256_update.h).
 //
 // Host code only validates parameters, looks up plans/kernels and enqueues work; every
 // byte of encode/decode output is produced by GPU kernels (kernels.hip, jit_codec.hip).
@@ -20,6 +20,7 @@
 
 #include "../../include/cauchy_256.h"
 #include "../../include/cauchy_256_batch.h"
+#include "../../include/cauchy_256_update.h"
 #include "field.hpp"
 #include "jit.hpp"
 #include "host_codec.hpp"
@@ -945,6 +946,41 @@ static int decode_batch_ptrs(int k, int m, int bytes, int stripes, uint8_t *cons
     return kOk;
 }
 
+// ------------------------------------------------------------------ recovery patch
+// cauchy_256_update_batch / _ptrs (include/cauchy_256_update.h): one launch of lh_update_kernel.
+// Every check comes before the device, so it holds without one.
+static int update_batch(int k, int m, int bytes, int stripes, int changes, const uint8_t *d_cols, UpdateArgs a,
+                        hipStream_t st) {
+    if (k < 1 || k > 255 || m < 1) return fail(kInvalid, "invalid k (1..255: a column is one byte, 0xFF reserved) or m");
+    if (bytes <= 0 || stripes < 0 || changes < 0 || changes > 255)
+        return fail(kInvalid, "invalid block_bytes, stripes or changes (0..255)");
+    const bool table = a.table != 0;
+    if (stripes > 0 && changes > 0 &&
+        (!d_cols || !(table ? (const void *)a.old_ptrs : (const void *)a.old_blocks) ||
+         !(table ? (const void *)a.rec_ptrs : (const void *)a.rec)))
+        return fail(kInvalid, "null cols, old or recovery argument");
+    if (!table) {
+        if (a.old_stride < (long long)changes * bytes || (a.new_blocks && a.new_stride < (long long)changes * bytes))
+            return fail(kInvalid, "old or new stride smaller than the stripe's changed blocks");
+        if (a.rec_stride < (long long)m * bytes) return fail(kInvalid, "recovery stride smaller than the stripe");
+    }
+    if (m > 1 && (k + m > 256 || bytes % 8 != 0)) return fail(kInvalid, "k + m > 256 or block_bytes % 8 != 0");
+    if (stripes == 0 || changes == 0) return kOk;
+    Device *d = nullptr;
+    if (int rc = current_device(&d)) return rc;
+    a.cols = d_cols;
+    a.k = k;
+    a.m = m;
+    a.changes = changes;
+    a.bytes = bytes;
+    a.stripes = stripes;
+    a.flat = (m == 1 || k == 1) ? 1 : 0;  // every coefficient is 1: the plain XOR of the deltas
+    if (!a.flat)
+        if (int rc = device_generator(d, k, m, &a.G, nullptr, st)) return rc;
+    LH_HIP(launch_update(a, st));  // (a batch of more than 2^31 - 1 workgroups: hipErrorInvalidValue)
+    return kOk;
+}
+
 // -------------------------------------------------------------- drop-in helpers
 // Where a drop-in block lives: host memory (pageable or pinned), memory the current device's
 // kernels may address directly (its own allocations; managed memory), or another device's
@@ -1495,6 +1531,39 @@ LH_API int cauchy_256_decode_batch_ptrs(int k, int m, int block_bytes, int strip
         lh::LaunchTrace trace;
         return lh::decode_batch_ptrs(k, m, block_bytes, stripes, (uint8_t *const *)d_block_ptrs, d_rows,
                                      (int8_t *)d_status, (hipStream_t)stream);
+    LH_CATCH
+}
+
+LH_API int cauchy_256_update_batch(int k, int m, int block_bytes, int stripes, int changes, const unsigned char *d_cols,
+                                   const void *d_old, long long old_stride, const void *d_new, long long new_stride,
+                                   void *d_recovery, long long recovery_stride, signed char *d_status, void *stream) {
+    LH_TRY
+        lh::LaunchTrace trace;
+        lh::UpdateArgs a{};
+        a.old_blocks = (const uint8_t *)d_old;
+        a.old_stride = old_stride;
+        a.new_blocks = (const uint8_t *)d_new;
+        a.new_stride = new_stride;
+        a.rec = (uint8_t *)d_recovery;
+        a.rec_stride = recovery_stride;
+        a.status = (int8_t *)d_status;
+        return lh::update_batch(k, m, block_bytes, stripes, changes, d_cols, a, (hipStream_t)stream);
+    LH_CATCH
+}
+
+LH_API int cauchy_256_update_batch_ptrs(int k, int m, int block_bytes, int stripes, int changes,
+                                        const unsigned char *d_cols, const void *const *d_old_ptrs,
+                                        const void *const *d_new_ptrs, void *const *d_recovery_ptrs,
+                                        signed char *d_status, void *stream) {
+    LH_TRY
+        lh::LaunchTrace trace;
+        lh::UpdateArgs a{};
+        a.old_ptrs = (const uint8_t *const *)d_old_ptrs;
+        a.new_ptrs = (const uint8_t *const *)d_new_ptrs;
+        a.rec_ptrs = (uint8_t *const *)d_recovery_ptrs;
+        a.status = (int8_t *)d_status;
+        a.table = 1;
+        return lh::update_batch(k, m, block_bytes, stripes, changes, d_cols, a, (hipStream_t)stream);
     LH_CATCH
 }
 

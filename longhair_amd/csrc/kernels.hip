@@ -12,6 +12,9 @@
 //                           run-time specialised kernels (jit_codec.hip) do not cover.
 //   lh_xor_reduce_kernel    out = XOR of n inputs for any block size (m == 1 encode
 //                           :1511-1522, k <= 1 copies :1501-1509, m == 1 decode :487-535).
+//   lh_update_kernel        recovery patch (cauchy_256_update_batch): recovery_r ^= sum_j
+//                           B(G[r][col_j]) (old_j ^ new_j) for the changed data blocks of a
+//                           stripe, the masked-XOR multiply with a per-lane coefficient.
 //   lh_scatter_kernel       moves recovered blocks from the workspace into their slots.
 //   lh_inverse_gt_kernel    large-m decode phase B (after the windowed phase A left V_r in
 //                           the recovery slots): D_E = A^-1 V by a computed jump into 256
@@ -202,6 +205,241 @@ __global__ void __launch_bounds__(256) lh_xor_reduce_kernel(lh::XorArgs a) {
             for (int r = 0; r < a.n_rep; ++r) out[(long long)r * a.bytes + q] = acc;
         }
     }
+}
+
+// ------------------------------------------------------------------ recovery patch
+// recovery_r ^= sum_j B(G[r][col_j]) delta_j (cauchy_256_update_batch): a read-modify-write
+// stream of (c or 2 c) + 2 m blocks per stripe against ~64 m c masked XORs per dword column,
+// an order of magnitude under the VALU roof, so the plain masked-XOR multiply of
+// lh_apply_generic_kernel serves, with the coefficient a per-lane value: lanes run flat over
+// (stripe, column chunk), neighbouring lanes may patch different columns of different stripes.
+//  * Every recovery byte belongs to exactly one lane (an overlapping last lane, harmless where
+//    the output is overwritten, would apply the delta twice): lane c of a stripe owns bytes
+//    [c W, min(c W + W, span)) of each sub-block, span = bytes / 8, W = kUpdateLane; or of the
+//    whole block (span = bytes, W = 16) when every coefficient is 1 (m == 1, k == 1: `flat`, any
+//    block size).  A whole lane moves its W bytes in one access at any alignment (wload).  The
+//    stripe's last lane, when span % W != 0, owns span % W bytes: it loads the W bytes that end
+//    the span beside its neighbours' loads (reading their bytes again harms nothing), computes
+//    at their width and stores its own bytes alone, in 8-, 4-, 2- and 1-byte accesses.  A span
+//    under W bytes is one lane that moves it piecewise both ways.
+//  * A stripe is all or nothing: every lane reads the stripe's `changes` column bytes first; a
+//    column in [k, 0xFE] makes all its lanes leave (status -1 from the stripe's lane 0), and so
+//    does a stripe of 0xFF entries only (status 0).
+//  * Output rows in tiles of kGenericTileOut, in a loop (m = 56 keeps 4 rows in registers): the
+//    tile's recovery words and the first delta are loaded before the arithmetic; later tiles
+//    find the deltas in the cache.
+//  * lad[q][y] = (B(2^q) delta)_y of the mul2 ladder is v[q + y] of one sequence of 15 words:
+//    v[0..7] = delta, v[8 + i] = v[i] ^ v[i + 1] ^ v[i + 2] ^ v[i + 7] (mul2's row 7).
+namespace {
+
+constexpr int kUpdateLane = 8;  // bytes per lane and sub-block
+
+// The first rem < W bytes at p (the rest zero) in 8-, 4-, 2- and 1-byte accesses.
+template <int W>
+__device__ __forceinline__ Word<W> wload_tail(const uint8_t *p, int rem) {
+    static_assert(W == 8 || W == 16, "two or four dwords");
+    Word<W> w;
+    wzero(w);
+    unsigned long long lo = 0;
+    const bool hi = W == 16 && (rem & 8);  // the rem % 8 bytes go behind 8 whole ones
+    if (hi) {
+        __builtin_memcpy(&lo, p, 8);
+        p += 8;
+    }
+    unsigned long long x = 0;
+    int o = 0;
+    if (rem & 4) {
+        uint32_t t;
+        __builtin_memcpy(&t, p, 4);
+        x = t;
+        o = 4;
+    }
+    if (rem & 2) {
+        uint16_t t;
+        __builtin_memcpy(&t, p + o, 2);
+        x |= (unsigned long long)t << (8 * o);
+        o += 2;
+    }
+    if (rem & 1) x |= (unsigned long long)p[o] << (8 * o);
+    if (!hi) lo = x;
+    w.v[0] = (uint32_t)lo;
+    w.v[1] = (uint32_t)(lo >> 32);
+    if (hi) {
+        w.v[W / 4 - 2] = (uint32_t)x;
+        w.v[W / 4 - 1] = (uint32_t)(x >> 32);
+    }
+    return w;
+}
+
+template <int W>
+__device__ __forceinline__ void wstore_tail(uint8_t *p, const Word<W> &w, int rem) {
+    static_assert(W == 8 || W == 16, "two or four dwords");
+    unsigned long long x = (unsigned long long)w.v[0] | ((unsigned long long)w.v[1] << 32);
+    if (W == 16 && (rem & 8)) {
+        __builtin_memcpy(p, &x, 8);
+        p += 8;
+        x = (unsigned long long)w.v[W / 4 - 2] | ((unsigned long long)w.v[W / 4 - 1] << 32);
+    }
+    if (rem & 4) {
+        const uint32_t t = (uint32_t)x;
+        __builtin_memcpy(p, &t, 4);
+        p += 4;
+        x >>= 32;
+    }
+    if (rem & 2) {
+        const uint16_t t = (uint16_t)x;
+        __builtin_memcpy(p, &t, 2);
+        p += 2;
+        x >>= 16;
+    }
+    if (rem & 1) *p = (uint8_t)x;
+}
+
+// w shifted down by n bytes (0 < n < W).
+template <int W>
+__device__ __forceinline__ Word<W> wshr_bytes(const Word<W> &w, int n) {
+    static_assert(W == 8 || W == 16, "two or four dwords");
+    unsigned long long lo = (unsigned long long)w.v[0] | ((unsigned long long)w.v[1] << 32), hi = 0;
+    if (W == 16) hi = (unsigned long long)w.v[W / 4 - 2] | ((unsigned long long)w.v[W / 4 - 1] << 32);
+    const int sh = 8 * n;
+    if (sh >= 64) {
+        lo = hi >> (sh - 64);
+        hi = 0;
+    } else {
+        lo = (lo >> sh) | (W == 16 ? hi << (64 - sh) : 0ull);
+        hi >>= sh;
+    }
+    Word<W> r;
+    r.v[0] = (uint32_t)lo;
+    r.v[1] = (uint32_t)(lo >> 32);
+    if (W == 16) {
+        r.v[W / 4 - 2] = (uint32_t)hi;
+        r.v[W / 4 - 1] = (uint32_t)(hi >> 32);
+    }
+    return r;
+}
+
+// A lane's column of the NS sub-blocks of one block, from byte `at` of each.  Every lane loads W
+// bytes in one access -- the stripe's last lane, when span % W != 0, the W bytes that end the
+// span (`at` = span - W): its own bytes are the top span % W, the others its neighbour's, which it
+// computes on and never stores.  Only a span under W bytes (uniform) is loaded piecewise.
+template <int W, int NS>
+__device__ __forceinline__ void lh_update_load(Word<W> (&d)[NS], const uint8_t *p, int at, int span) {
+    if (span >= W) {
+#pragma unroll
+        for (int y = 0; y < NS; ++y) d[y] = wload<W>(p + (long long)y * span + at);
+    } else {
+#pragma unroll
+        for (int y = 0; y < NS; ++y) d[y] = wload_tail<W>(p + (long long)y * span, span);
+    }
+}
+
+// The lane's own bytes back, from byte c * W of each sub-block: W, or the last lane's span % W
+// (the top bytes of its window) piecewise.
+template <int W, int NS>
+__device__ __forceinline__ void lh_update_store(uint8_t *p, const Word<W> (&d)[NS], int c, int span) {
+    const int rem = span % W;
+    if (c * W + W <= span) {
+#pragma unroll
+        for (int y = 0; y < NS; ++y) wstore<W>(p + (long long)y * span + c * W, d[y]);
+    } else {
+#pragma unroll
+        for (int y = 0; y < NS; ++y)
+            wstore_tail<W>(p + (long long)y * span + c * W, span >= W ? wshr_bytes<W>(d[y], W - rem) : d[y], rem);
+    }
+}
+
+// Lane c of stripe s, over NS sub-blocks (8, or 1: flat).
+template <int W, int NS, bool PTR>
+__device__ __forceinline__ void lh_update_lane(const lh::UpdateArgs &a, long long s, int c) {
+    constexpr int TO = lh::kGenericTileOut;
+    const int at = min(c * W, max(a.span - W, 0));  // (the last lane's window ends with the span)
+    const long long e0 = s * a.changes;
+    const bool two = PTR ? a.new_ptrs != nullptr : a.new_blocks != nullptr;
+    for (int i0 = 0; i0 < a.m; i0 += TO) {
+        const int ni = min(TO, a.m - i0);
+        uint8_t *out[TO];
+        Word<W> acc[TO][NS];
+#pragma unroll
+        for (int i = 0; i < TO; ++i) {
+            if (i < ni) {
+                out[i] = PTR ? a.rec_ptrs[s * a.m + i0 + i] : a.rec + s * a.rec_stride + (long long)(i0 + i) * a.bytes;
+                lh_update_load<W, NS>(acc[i], out[i], at, a.span);
+            }
+        }
+        for (int j = 0; j < a.changes; ++j) {
+            const uint32_t col = a.cols[e0 + j];
+            if (col == 0xFFu) continue;  // no change in this entry: its blocks are not read
+            Word<W> v[2 * NS - 1];
+            {
+                Word<W> d[NS];
+                lh_update_load<W, NS>(d, PTR ? a.old_ptrs[e0 + j] : a.old_blocks + s * a.old_stride + (long long)j * a.bytes, at,
+                                      a.span);
+#pragma unroll
+                for (int y = 0; y < NS; ++y) v[y] = d[y];
+                if (two) {
+                    lh_update_load<W, NS>(d, PTR ? a.new_ptrs[e0 + j] : a.new_blocks + s * a.new_stride + (long long)j * a.bytes,
+                                          at, a.span);
+#pragma unroll
+                    for (int y = 0; y < NS; ++y) wxor(v[y], d[y]);
+                }
+            }
+            if constexpr (NS == 8) {
+#pragma unroll
+                for (int q = 0; q < 7; ++q)
+#pragma unroll
+                    for (int w = 0; w < Word<W>::N; ++w) {
+                        v[8 + q].v[w] = v[q].v[w] ^ v[q + 1].v[w] ^ v[q + 2].v[w] ^ v[q + 7].v[w];
+                        // (a value of its own: folded into the sums below it costs more XORs, not fewer)
+                        asm volatile("" : "+v"(v[8 + q].v[w]));
+                    }
+#pragma unroll
+                for (int i = 0; i < TO; ++i) {
+                    if (i < ni) {
+                        const uint32_t e = a.G[(long long)(i0 + i) * a.k + col];
+#pragma unroll
+                        for (int q = 0; q < 8; ++q) {
+                            const uint32_t mask = 0u - ((e >> q) & 1u);
+#pragma unroll
+                            for (int y = 0; y < 8; ++y)
+#pragma unroll
+                            for (int w = 0; w < Word<W>::N; ++w)  // acc ^= v & mask, as one instruction
+                                acc[i][y].v[w] = __builtin_amdgcn_bitop3_b32(mask, acc[i][y].v[w], v[q + y].v[w], 0x6c);
+                        }
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < TO; ++i)
+                    if (i < ni) wxor(acc[i][0], v[0]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < TO; ++i)
+            if (i < ni) lh_update_store<W, NS>(out[i], acc[i], c, a.span);
+    }
+}
+
+}  // namespace
+
+template <bool PTR>
+__global__ void __launch_bounds__(256) lh_update_kernel(lh::UpdateArgs a) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long s = t / a.nch;
+    if (s >= a.stripes) return;
+    const int c = (int)(t - s * a.nch);
+    bool bad = false, any = false;
+    for (int j = 0; j < a.changes; ++j) {
+        const int col = a.cols[s * a.changes + j];
+        if (col != 0xFF) {
+            any = true;
+            if (col >= a.k) bad = true;
+        }
+    }
+    if (c == 0 && a.status) a.status[s] = bad ? -1 : 0;
+    if (bad || !any) return;
+    if (a.flat) lh_update_lane<16, 1, PTR>(a, s, c);
+    else lh_update_lane<kUpdateLane, 8, PTR>(a, s, c);
 }
 
 // ------------------------------------------------------------------------ scatter
@@ -1523,6 +1761,24 @@ hipError_t launch_ptr_copy(const PtrCopyArgs &a, hipStream_t st) {
     if ((waves + 3) / 4 > 0x7FFFFFFF) return hipErrorInvalidValue;
     hipLaunchKernelGGL(lh_ptr_copy_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, a);
     note_launch(a.scatter ? "lh_ptr_copy_kernel(scatter)" : "lh_ptr_copy_kernel(gather)");
+    return hipGetLastError();
+}
+
+hipError_t launch_update(const UpdateArgs &a, hipStream_t st) {
+    if (a.k < 1 || a.k > 255 || a.m < 1 || a.changes < 1 || a.changes > 255 || a.bytes < 1 ||
+        (!a.flat && a.bytes % 8 != 0))
+        return hipErrorInvalidValue;
+    UpdateArgs g = a;
+    g.span = a.flat ? a.bytes : a.bytes / 8;
+    const int lane = a.flat ? 16 : kUpdateLane;
+    g.nch = (g.span + lane - 1) / lane;
+    const long long lanes = (long long)a.stripes * g.nch;
+    if (lanes <= 0) return hipSuccess;
+    if ((lanes + 255) / 256 > 0x7FFFFFFF) return hipErrorInvalidValue;
+    const bool ptr = a.table != 0;
+    hipLaunchKernelGGL(ptr ? lh_update_kernel<true> : lh_update_kernel<false>, dim3((unsigned)((lanes + 255) / 256)),
+                       dim3(256), 0, st, g);
+    note_launch(ptr ? "lh_update_kernel(pointer table)" : "lh_update_kernel");
     return hipGetLastError();
 }
 

@@ -182,6 +182,33 @@ struct PtrCopyArgs {
     int n, ncopy, bytes, stripes, scatter;
 };
 
+// Recovery patch (cauchy_256_update_batch, lh_update_kernel): recovery_r ^= sum_j
+// B(G[r][cols[j]]) delta_j over the stripe's `changes` entries, delta_j = old_j ^ new_j (or
+// old_j alone without `new`).  An entry with column 0xFF is skipped; a column in [k, 0xFE]
+// invalidates the stripe (status -1, nothing written).
+struct UpdateArgs {
+    const uint8_t *cols;          // cols[s*changes + j]
+    const uint8_t *old_blocks;    // change j of stripe s: old_blocks + s*old_stride + j*bytes
+    long long old_stride;
+    const uint8_t *new_blocks;    // likewise, or NULL: old_blocks holds the deltas
+    long long new_stride;
+    uint8_t *rec;                 // recovery block r of stripe s: rec + s*rec_stride + r*bytes
+    long long rec_stride;
+    // table != 0: pointer tables (cauchy_256_update_batch_ptrs; the strided fields unused):
+    // change j of stripe s at old_ptrs[s*changes + j] (new_ptrs likewise, or NULL), recovery
+    // block r at rec_ptrs[s*m + r]
+    int table;
+    const uint8_t *const *old_ptrs;
+    const uint8_t *const *new_ptrs;
+    uint8_t *const *rec_ptrs;
+    int8_t *status;               // optional, stripes
+    const uint8_t *G;             // m x k generator (row 0 = ones); unused when `flat`
+    int k, m, changes, bytes, stripes;
+    int flat;                     // m == 1 or k == 1: every coefficient is 1, lanes over the block's bytes
+    int span, nch;                // set by launch_update: bytes a lane column runs over (bytes / 8 of each
+                                  // sub-block, or the whole block when flat) and lanes per stripe
+};
+
 // Launch trace (codec.cpp): every launch site records the kernel it enqueued, so the
 // calling thread can ask which kernels its last batch call ran (cauchy_256_last_launch).
 void note_launch(const char *kernel);
@@ -199,5 +226,6 @@ hipError_t launch_xor_reduce(const XorArgs &a, hipStream_t st);
 hipError_t launch_scatter(const ScatterArgs &a, hipStream_t st);
 hipError_t launch_plan(const PlanArgs &a, hipStream_t st);
 hipError_t launch_ptr_copy(const PtrCopyArgs &a, hipStream_t st);
+hipError_t launch_update(const UpdateArgs &a, hipStream_t st);
 
 }  // namespace lh
