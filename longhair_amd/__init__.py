@@ -7,8 +7,9 @@ Python view of the C-ABI library `liblonghair_amd.so` (built from longhair_amd/c
   `cauchy_256_init()`, `cauchy_256_encode(k, m, data_ptrs, recovery_blocks, block_bytes)`,
   `cauchy_256_decode(k, m, blocks, block_bytes)` and the `Block` structure, taking the same
   arguments as the C functions (ctypes pointers / arrays) and returning the same codes;
-* batched device-resident helpers on torch uint8 tensors: `encode_batch`, `decode_batch`, and
-  `update_batch`, which patches the recovery blocks after a few data blocks changed.
+* batched device-resident helpers on torch uint8 tensors: `encode_batch`, `decode_batch`,
+  `update_batch`, which patches the recovery blocks after a few data blocks changed, and
+  `verify_batch`, which tells whether stored recovery blocks still belong to the stored data.
 
 There is no CPU implementation: importing works without a GPU, but every codec call
 goes through the HIP library and fails loudly (LonghairError / non-zero codes) when no
@@ -253,6 +254,62 @@ def update_batch_ptrs(k, m, block_bytes, cols, old_ptrs, new_ptrs, recovery_ptrs
                                             ctypes.c_void_p(_stream_handle(stream)))
     if rc != 0:
         raise LonghairError(rc, "cauchy_256_update_batch_ptrs")
+    return status
+
+
+def _verify_outputs(stripes, m, status, bad_rows, device):
+    import torch
+    if status is None:
+        status = torch.empty((stripes,), dtype=torch.int8, device=device)
+    _cuda_tensor(status, torch.int8, "status", (stripes,), True, device)
+    if bad_rows is not None:
+        _cuda_tensor(bad_rows, torch.uint8, "bad_rows", (stripes, m), True, device)
+    return status, ctypes.c_void_p(bad_rows.data_ptr()) if bad_rows is not None else None
+
+
+def verify_batch(data, recovery, status=None, bad_rows=None, stream=None):
+    """Check stored recovery blocks against stored data (cauchy_256_verify_batch): one pass over
+    the k + m blocks of each stripe, no scratch.
+
+    data:     uint8 CUDA tensor [stripes, k, block_bytes];
+    recovery: uint8 CUDA tensor [stripes, m, block_bytes]; both are only read;
+    bad_rows: optional uint8 CUDA tensor [stripes, m], contiguous: 1 where recovery row r differs
+              from what encode_batch writes for the stored data, else 0.
+    Returns `status` (int8 [stripes], allocated if not given): 0 every row intact, 1 some row bad."""
+    _block_tensor(data, "data")
+    _block_tensor(recovery, "recovery")
+    stripes, k, nbytes = data.shape
+    m = recovery.shape[1]
+    _require(tuple(recovery.shape) == (stripes, m, nbytes), f"recovery must be [{stripes}, m, {nbytes}]")
+    _require(recovery.device == data.device, "recovery must be on data's device")
+    status, rows_p = _verify_outputs(stripes, m, status, bad_rows, data.device)
+    rc = lib().cauchy_256_verify_batch(k, m, nbytes, stripes, ctypes.c_void_p(data.data_ptr()),
+                                       ctypes.c_longlong(data.stride(0)), ctypes.c_void_p(recovery.data_ptr()),
+                                       ctypes.c_longlong(recovery.stride(0)), ctypes.c_void_p(status.data_ptr()),
+                                       rows_p, ctypes.c_void_p(_stream_handle(stream)))
+    if rc != 0:
+        raise LonghairError(rc, "cauchy_256_verify_batch")
+    return status
+
+
+def verify_batch_ptrs(k, m, block_bytes, data_ptrs, recovery_ptrs, status=None, bad_rows=None, stream=None):
+    """verify_batch for blocks that sit anywhere in device memory (cauchy_256_verify_batch_ptrs).
+
+    data_ptrs:     int64 CUDA tensor [stripes, k] of device addresses;
+    recovery_ptrs: int64 CUDA tensor [stripes, m].
+    Returns `status` (int8 [stripes]); `bad_rows` (uint8 [stripes, m]) is filled when given."""
+    import torch
+    _cuda_tensor(data_ptrs, torch.int64, "data_ptrs")
+    _require(data_ptrs.dim() == 2, "data_ptrs must be [stripes, k]")
+    stripes = data_ptrs.shape[0]
+    data_t = _ptr_table(data_ptrs, stripes, k, "data_ptrs")
+    rec_t = _ptr_table(recovery_ptrs, stripes, m, "recovery_ptrs")
+    _require(recovery_ptrs.device == data_ptrs.device, "recovery_ptrs must be on data_ptrs' device")
+    status, rows_p = _verify_outputs(stripes, m, status, bad_rows, data_ptrs.device)
+    rc = lib().cauchy_256_verify_batch_ptrs(k, m, block_bytes, stripes, data_t, rec_t, ctypes.c_void_p(status.data_ptr()),
+                                            rows_p, ctypes.c_void_p(_stream_handle(stream)))
+    if rc != 0:
+        raise LonghairError(rc, "cauchy_256_verify_batch_ptrs")
     return status
 
 

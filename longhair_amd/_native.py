@@ -71,12 +71,21 @@ UPDATE_EXPORTS = {
                                                     ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
 }
+# Every symbol include/cauchy_256_verify.h declares (the recovery scrub), in both libraries.
+VERIFY_EXPORTS = {
+    "cauchy_256_verify_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
+                                               ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "cauchy_256_verify_batch_ptrs": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_void_p]),
+}
 
 
 def bind(l):
-    """Set the ctypes signatures of a loaded copy of the library (every EXPORTS and
-    UPDATE_EXPORTS symbol must exist; OPTIONAL_EXPORTS where present)."""
-    for name, (res, args) in list(EXPORTS.items()) + list(UPDATE_EXPORTS.items()):
+    """Set the ctypes signatures of a loaded copy of the library (every EXPORTS, UPDATE_EXPORTS
+    and VERIFY_EXPORTS symbol must exist; OPTIONAL_EXPORTS where present)."""
+    for name, (res, args) in list(EXPORTS.items()) + list(UPDATE_EXPORTS.items()) + list(VERIFY_EXPORTS.items()):
         f = getattr(l, name)
         f.restype = res
         f.argtypes = args

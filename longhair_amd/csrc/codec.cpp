@@ -1,5 +1,5 @@
 // codec.cpp -- the C ABI: drop-in cauchy_256.h entry points and the batched
-// device-resident extension (cauchy_256_batch.h, cauchy_256_update.h).
+// device-resident extension (cauchy_256_batch.h, cauchy_256_update.h, cauchy_256_verify.h).
 //
 // Host code only validates parameters, looks up plans/kernels and enqueues work; every
 // byte of encode/decode output is produced by GPU kernels (kernels.hip, jit_codec.hip).
@@ -21,6 +21,7 @@
 #include "../../include/cauchy_256.h"
 #include "../../include/cauchy_256_batch.h"
 #include "../../include/cauchy_256_update.h"
+#include "../../include/cauchy_256_verify.h"
 #include "field.hpp"
 #include "jit.hpp"
 #include "host_codec.hpp"
@@ -981,6 +982,41 @@ static int update_batch(int k, int m, int bytes, int stripes, int changes, const
     return kOk;
 }
 
+// ------------------------------------------------------------------ recovery scrub
+// cauchy_256_verify_batch / _ptrs (include/cauchy_256_verify.h): two clearing copies and one launch of
+// lh_verify_kernel.  Every check comes before the device, so it holds without one.
+static int verify_batch(int k, int m, int bytes, int stripes, VerifyArgs a, hipStream_t st) {
+    if (k < 1 || k > 256 || m < 1 || m > 256) return fail(kInvalid, "invalid k or m (1..256)");
+    if (bytes <= 0 || stripes < 0) return fail(kInvalid, "invalid block_bytes or stripes");
+    if (m > 1 && k > 1 && (k + m > 256 || bytes % 8 != 0)) return fail(kInvalid, "k + m > 256 or block_bytes % 8 != 0");
+    const bool table = a.table != 0;
+    if (!table) {
+        if (a.data_stride < (long long)k * bytes) return fail(kInvalid, "data stride smaller than the stripe");
+        if (a.rec_stride < (long long)m * bytes) return fail(kInvalid, "recovery stride smaller than the stripe");
+    }
+    if (!a.status && !a.bad_rows) return fail(kInvalid, "null status and bad_rows: no output");
+    if (stripes > 0 && (!(table ? (const void *)a.data_ptrs : (const void *)a.data) ||
+                        !(table ? (const void *)a.rec_ptrs : (const void *)a.rec)))
+        return fail(kInvalid, "null data or recovery argument");
+    if (stripes == 0) return kOk;
+    Device *d = nullptr;
+    if (int rc = current_device(&d)) return rc;
+    a.k = k;
+    a.m = m;
+    a.bytes = bytes;
+    a.stripes = stripes;
+    a.flat = (m == 1 || k == 1) ? 1 : 0;  // every coefficient is 1: recovery_r against the XOR of the data
+    if (!a.flat)
+        if (int rc = device_generator(d, k, m, &a.G, nullptr, st)) return rc;
+    // launch_verify zeroes both outputs by copies from the zero page (grown by doubling: few
+    // retired pages; under capture it must be large enough already)
+    size_t need = 64;
+    while (need < (size_t)stripes * (a.bad_rows ? m : 1)) need *= 2;
+    if (int rc = zero_page(d, need, &a.zero, st)) return rc;
+    LH_HIP(launch_verify(a, st));  // (a batch of more than 2^31 - 1 workgroups: hipErrorInvalidValue)
+    return kOk;
+}
+
 // -------------------------------------------------------------- drop-in helpers
 // Where a drop-in block lives: host memory (pageable or pinned), memory the current device's
 // kernels may address directly (its own allocations; managed memory), or another device's
@@ -1564,6 +1600,37 @@ LH_API int cauchy_256_update_batch_ptrs(int k, int m, int block_bytes, int strip
         a.status = (int8_t *)d_status;
         a.table = 1;
         return lh::update_batch(k, m, block_bytes, stripes, changes, d_cols, a, (hipStream_t)stream);
+    LH_CATCH
+}
+
+LH_API int cauchy_256_verify_batch(int k, int m, int block_bytes, int stripes, const void *d_data, long long data_stride,
+                                   const void *d_recovery, long long recovery_stride, signed char *d_status,
+                                   unsigned char *d_bad_rows, void *stream) {
+    LH_TRY
+        lh::LaunchTrace trace;
+        lh::VerifyArgs a{};
+        a.data = (const uint8_t *)d_data;
+        a.data_stride = data_stride;
+        a.rec = (const uint8_t *)d_recovery;
+        a.rec_stride = recovery_stride;
+        a.status = (int8_t *)d_status;
+        a.bad_rows = d_bad_rows;
+        return lh::verify_batch(k, m, block_bytes, stripes, a, (hipStream_t)stream);
+    LH_CATCH
+}
+
+LH_API int cauchy_256_verify_batch_ptrs(int k, int m, int block_bytes, int stripes, const void *const *d_data_ptrs,
+                                        const void *const *d_recovery_ptrs, signed char *d_status,
+                                        unsigned char *d_bad_rows, void *stream) {
+    LH_TRY
+        lh::LaunchTrace trace;
+        lh::VerifyArgs a{};
+        a.data_ptrs = (const uint8_t *const *)d_data_ptrs;
+        a.rec_ptrs = (const uint8_t *const *)d_recovery_ptrs;
+        a.status = (int8_t *)d_status;
+        a.bad_rows = d_bad_rows;
+        a.table = 1;
+        return lh::verify_batch(k, m, block_bytes, stripes, a, (hipStream_t)stream);
     LH_CATCH
 }
 

@@ -15,6 +15,9 @@
 //   lh_update_kernel        recovery patch (cauchy_256_update_batch): recovery_r ^= sum_j
 //                           B(G[r][col_j]) (old_j ^ new_j) for the changed data blocks of a
 //                           stripe, the masked-XOR multiply with a per-lane coefficient.
+//   lh_verify_kernel        recovery scrub (cauchy_256_verify_batch): is recovery_r ^ sum_j
+//                           B(G[r][j]) data_j zero for every row of a stripe?  The update's
+//                           multiply with a wave-uniform coefficient, nothing stored but flags.
 //   lh_scatter_kernel       moves recovered blocks from the workspace into their slots.
 //   lh_inverse_gt_kernel    large-m decode phase B (after the windowed phase A left V_r in
 //                           the recovery slots): D_E = A^-1 V by a computed jump into 256
@@ -349,6 +352,43 @@ __device__ __forceinline__ void lh_update_store(uint8_t *p, const Word<W> (&d)[N
     }
 }
 
+// v[0..7] = a column's words of the 8 sub-blocks: fills v[8 + i] = v[i] ^ v[i + 1] ^ v[i + 2] ^ v[i + 7],
+// so that (B(2^q) column)_y = v[q + y].
+template <int W>
+__device__ __forceinline__ void lh_ladder(Word<W> (&v)[15]) {
+#pragma unroll
+    for (int q = 0; q < 7; ++q)
+#pragma unroll
+        for (int w = 0; w < Word<W>::N; ++w) {
+            v[8 + q].v[w] = v[q].v[w] ^ v[q + 1].v[w] ^ v[q + 2].v[w] ^ v[q + 7].v[w];
+            // (a value of its own: folded into the sums below it costs more XORs, not fewer)
+            asm volatile("" : "+v"(v[8 + q].v[w]));
+        }
+}
+
+// acc ^= B(e) column over the ladder v: one masked XOR (acc ^= v & mask, one v_bitop3_b32) per
+// coefficient bit, sub-block and dword.  SKIP (e wave-uniform, a scalar): a zero bit is a
+// uniform branch around its 8 rows of plain XORs.
+template <int W, bool SKIP>
+__device__ __forceinline__ void lh_mul_acc(Word<W> (&acc)[8], const Word<W> (&v)[15], uint32_t e) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        if constexpr (SKIP) {
+            if ((e >> q) & 1u) {
+#pragma unroll
+                for (int y = 0; y < 8; ++y) wxor(acc[y], v[q + y]);
+            }
+        } else {
+            const uint32_t mask = 0u - ((e >> q) & 1u);
+#pragma unroll
+            for (int y = 0; y < 8; ++y)
+#pragma unroll
+                for (int w = 0; w < Word<W>::N; ++w)
+                    acc[y].v[w] = __builtin_amdgcn_bitop3_b32(mask, acc[y].v[w], v[q + y].v[w], 0x6c);
+        }
+    }
+}
+
 // Lane c of stripe s, over NS sub-blocks (8, or 1: flat).
 template <int W, int NS, bool PTR>
 __device__ __forceinline__ void lh_update_lane(const lh::UpdateArgs &a, long long s, int c) {
@@ -385,29 +425,10 @@ __device__ __forceinline__ void lh_update_lane(const lh::UpdateArgs &a, long lon
                 }
             }
             if constexpr (NS == 8) {
+                lh_ladder<W>(v);
 #pragma unroll
-                for (int q = 0; q < 7; ++q)
-#pragma unroll
-                    for (int w = 0; w < Word<W>::N; ++w) {
-                        v[8 + q].v[w] = v[q].v[w] ^ v[q + 1].v[w] ^ v[q + 2].v[w] ^ v[q + 7].v[w];
-                        // (a value of its own: folded into the sums below it costs more XORs, not fewer)
-                        asm volatile("" : "+v"(v[8 + q].v[w]));
-                    }
-#pragma unroll
-                for (int i = 0; i < TO; ++i) {
-                    if (i < ni) {
-                        const uint32_t e = a.G[(long long)(i0 + i) * a.k + col];
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) {
-                            const uint32_t mask = 0u - ((e >> q) & 1u);
-#pragma unroll
-                            for (int y = 0; y < 8; ++y)
-#pragma unroll
-                            for (int w = 0; w < Word<W>::N; ++w)  // acc ^= v & mask, as one instruction
-                                acc[i][y].v[w] = __builtin_amdgcn_bitop3_b32(mask, acc[i][y].v[w], v[q + y].v[w], 0x6c);
-                        }
-                    }
-                }
+                for (int i = 0; i < TO; ++i)
+                    if (i < ni) lh_mul_acc<W, false>(acc[i], v, a.G[(long long)(i0 + i) * a.k + col]);
             } else {
 #pragma unroll
                 for (int i = 0; i < TO; ++i)
@@ -440,6 +461,136 @@ __global__ void __launch_bounds__(256) lh_update_kernel(lh::UpdateArgs a) {
     if (bad || !any) return;
     if (a.flat) lh_update_lane<16, 1, PTR>(a, s, c);
     else lh_update_lane<kUpdateLane, 8, PTR>(a, s, c);
+}
+
+// ------------------------------------------------------------------ recovery scrub
+// cauchy_256_verify_batch: row r of a stripe is intact iff its syndrome recovery_r ^ sum_j
+// B(G[r][j]) data_j is zero.  The update's accumulation over all k columns, from the stored
+// recovery words to "is any bit set": k + m blocks read, one byte stored per bad row and stripe
+// into outputs the launcher zeroed on the same stream (every writer of a byte writes 1, so no
+// atomics), no scratch.
+//  * Lanes as in lh_update_kernel: flat over (stripe, 8-byte column of each sub-block).  Nothing
+//    is stored back, so the stripe's last lane, when span % 8 != 0, just takes the 8 bytes that
+//    end the span (comparing its neighbour's bytes again harms nothing); a span under 8 bytes is
+//    loaded piecewise, data and recovery zero-padded alike.
+//  * The column is the loop index and G is the same for every stripe, so G[r][j] is wave-uniform:
+//    a scalar (readfirstlane), and a zero coefficient bit a uniform branch around its 16 XORs
+//    (half the bits of a Cauchy coefficient on average: 8.2 against 16.0 ms with the masked
+//    form at k128/m32/8192 x 8 192).  The next column's words and coefficients
+//    are loaded before the current one is combined.
+//  * A row tile (kGenericTileOut rows) per workgroup; the tiles of one 256-lane chunk are
+//    workgroups b, b + 8, b + 16, ... of the grid, which the hardware places on one XCD at about
+//    the same time, so the chunk's data is read from memory once and by the other tiles from that
+//    XCD's L2 (placement is for speed only; looped in the lane instead the same shape took 12.9
+//    ms against 8.2, and k200/m56/65536 x 64, one wave per SIMD that way, 4.5 against 1.5).  The
+//    grid is padded to whole groups of 8 chunks; with `tiles` == 1 it is the update's.
+//  * m == 1, k == 1 (`flat`, any block size): 16-byte lanes over the whole block, the XOR of the
+//    data columns once, compared with each recovery row.
+namespace {
+
+__device__ __forceinline__ void lh_verify_flag(const lh::VerifyArgs &a, long long s, int r) {
+    if (a.bad_rows) a.bad_rows[s * a.m + r] = 1;
+    if (a.status) a.status[s] = 1;
+}
+
+template <bool PTR>
+__device__ __forceinline__ const uint8_t *lh_verify_data(const lh::VerifyArgs &a, long long s, int j) {
+    return PTR ? a.data_ptrs[s * a.k + j] : a.data + s * a.data_stride + (long long)j * a.bytes;
+}
+
+template <bool PTR>
+__device__ __forceinline__ const uint8_t *lh_verify_rec(const lh::VerifyArgs &a, long long s, int r) {
+    return PTR ? a.rec_ptrs[s * a.m + r] : a.rec + s * a.rec_stride + (long long)r * a.bytes;
+}
+
+// Rows [i0, i0 + ni) of lane c of stripe s.
+template <int W, bool PTR>
+__device__ __forceinline__ void lh_verify_lane(const lh::VerifyArgs &a, long long s, int c, int i0, int ni) {
+    constexpr int TO = lh::kGenericTileOut;
+    const int at = min(c * W, max(a.span - W, 0));  // (the last lane's window ends with the span)
+    Word<W> acc[TO][8];
+#pragma unroll
+    for (int i = 0; i < TO; ++i)
+        if (i < ni) lh_update_load<W, 8>(acc[i], lh_verify_rec<PTR>(a, s, i0 + i), at, a.span);
+    const uint8_t *g = a.G + (long long)i0 * a.k;
+    Word<W> cur[8];
+    uint32_t e[TO];
+    lh_update_load<W, 8>(cur, lh_verify_data<PTR>(a, s, 0), at, a.span);
+#pragma unroll
+    for (int i = 0; i < TO; ++i) e[i] = i < ni ? g[i * a.k] : 0;
+    for (int j = 0; j < a.k; ++j) {
+        const int jn = j + 1 < a.k ? j + 1 : j;  // (the last column reloads itself)
+        Word<W> nxt[8];
+        uint32_t en[TO];
+        lh_update_load<W, 8>(nxt, lh_verify_data<PTR>(a, s, jn), at, a.span);
+#pragma unroll
+        for (int i = 0; i < TO; ++i) en[i] = i < ni ? g[i * a.k + jn] : 0;
+        Word<W> v[15];
+#pragma unroll
+        for (int y = 0; y < 8; ++y) v[y] = cur[y];
+        lh_ladder<W>(v);
+#pragma unroll
+        for (int i = 0; i < TO; ++i)
+            if (i < ni)
+                lh_mul_acc<W, true>(acc[i], v, (uint32_t)__builtin_amdgcn_readfirstlane((int)e[i]));
+#pragma unroll
+        for (int y = 0; y < 8; ++y) cur[y] = nxt[y];
+#pragma unroll
+        for (int i = 0; i < TO; ++i) e[i] = en[i];
+    }
+#pragma unroll
+    for (int i = 0; i < TO; ++i) {
+        if (i < ni) {
+            uint32_t any = 0;
+#pragma unroll
+            for (int y = 0; y < 8; ++y)
+#pragma unroll
+                for (int w = 0; w < Word<W>::N; ++w) any |= acc[i][y].v[w];
+            if (any) lh_verify_flag(a, s, i0 + i);
+        }
+    }
+}
+
+template <bool PTR>
+__device__ __forceinline__ void lh_verify_flat(const lh::VerifyArgs &a, long long s, int c) {
+    constexpr int W = 16;
+    const int at = min(c * W, max(a.span - W, 0));
+    Word<W> x[1], d[1];
+    wzero(x[0]);
+    for (int j = 0; j < a.k; ++j) {
+        lh_update_load<W, 1>(d, lh_verify_data<PTR>(a, s, j), at, a.span);
+        wxor(x[0], d[0]);
+    }
+    for (int r = 0; r < a.m; ++r) {
+        lh_update_load<W, 1>(d, lh_verify_rec<PTR>(a, s, r), at, a.span);
+        uint32_t any = 0;
+#pragma unroll
+        for (int w = 0; w < Word<W>::N; ++w) any |= d[0].v[w] ^ x[0].v[w];
+        if (any) lh_verify_flag(a, s, r);
+    }
+}
+
+}  // namespace
+
+template <bool PTR>
+__global__ void __launch_bounds__(256) lh_verify_kernel(lh::VerifyArgs a) {
+    constexpr int TO = lh::kGenericTileOut;
+    long long chunk = blockIdx.x;
+    int tile = 0;
+    if (a.tiles > 1) {  // workgroups b, b + 8, ...: the tiles of chunk (b / (8 tiles)) * 8 + b % 8
+        const long long q = chunk >> 3;
+        tile = (int)(q % a.tiles);
+        chunk = (q / a.tiles) * 8 + (chunk & 7);
+    }
+    const long long t = chunk * 256 + threadIdx.x;
+    const long long s = t / a.nch;
+    if (s >= a.stripes) return;
+    const int c = (int)(t - s * a.nch);
+    if (a.flat) {
+        lh_verify_flat<PTR>(a, s, c);
+        return;
+    }
+    lh_verify_lane<kUpdateLane, PTR>(a, s, c, tile * TO, min(TO, a.m - tile * TO));
 }
 
 // ------------------------------------------------------------------------ scatter
@@ -1779,6 +1930,35 @@ hipError_t launch_update(const UpdateArgs &a, hipStream_t st) {
     hipLaunchKernelGGL(ptr ? lh_update_kernel<true> : lh_update_kernel<false>, dim3((unsigned)((lanes + 255) / 256)),
                        dim3(256), 0, st, g);
     note_launch(ptr ? "lh_update_kernel(pointer table)" : "lh_update_kernel");
+    return hipGetLastError();
+}
+
+hipError_t launch_verify(const VerifyArgs &a, hipStream_t st) {
+    if (a.k < 1 || a.m < 1 || a.bytes < 1 || (!a.flat && a.bytes % 8 != 0) || (!a.status && !a.bad_rows) || !a.zero)
+        return hipErrorInvalidValue;
+    VerifyArgs g = a;
+    g.span = a.flat ? a.bytes : a.bytes / 8;
+    const int lane = a.flat ? 16 : kUpdateLane;
+    g.nch = (g.span + lane - 1) / lane;
+    const long long lanes = (long long)a.stripes * g.nch;
+    if (lanes <= 0) return hipSuccess;
+    long long groups = (lanes + 255) / 256;
+    g.tiles = a.flat ? 1 : (a.m + kGenericTileOut - 1) / kGenericTileOut;
+    if (g.tiles > 1) groups = (groups + 7) / 8 * 8 * g.tiles;
+    if (groups > 0x7FFFFFFF) return hipErrorInvalidValue;
+    // The kernel stores only the 1s: both outputs start from zero, by device-to-device copies
+    // from the zero page in front of the kernel on the same stream (copy nodes under capture).
+    // Not hipMemsetAsync: captured, its node zeroes on the first replay and on later ones writes
+    // stray bytes into the destination for some sizes (24 and 96 bytes among them, ROCm 7.2);
+    // copy nodes of every size tried replay correctly.
+    hipError_t e = hipSuccess;
+    if (a.status) e = hipMemcpyAsync(a.status, a.zero, (size_t)a.stripes, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && a.bad_rows)
+        e = hipMemcpyAsync(a.bad_rows, a.zero, (size_t)a.stripes * a.m, hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) return e;
+    const bool ptr = a.table != 0;
+    hipLaunchKernelGGL(ptr ? lh_verify_kernel<true> : lh_verify_kernel<false>, dim3((unsigned)groups), dim3(256), 0, st, g);
+    note_launch(ptr ? "lh_verify_kernel(pointer table)" : "lh_verify_kernel");
     return hipGetLastError();
 }
 

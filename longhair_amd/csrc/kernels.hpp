@@ -209,6 +209,28 @@ struct UpdateArgs {
                                   // sub-block, or the whole block when flat) and lanes per stripe
 };
 
+// Recovery scrub (cauchy_256_verify_batch, lh_verify_kernel): row r of stripe s is bad iff
+// recovery_r ^ sum_j B(G[r][j]) data_j != 0 over all k data blocks.  Reads only; stores the byte 1
+// to bad_rows[s*m + r] and status[s] of a bad row (launch_verify zeroes both outputs first).
+struct VerifyArgs {
+    const uint8_t *data;          // data block j of stripe s: data + s*data_stride + j*bytes
+    long long data_stride;
+    const uint8_t *rec;           // recovery block r of stripe s: rec + s*rec_stride + r*bytes
+    long long rec_stride;
+    // table != 0: pointer tables (cauchy_256_verify_batch_ptrs; the strided fields unused): data
+    // block j of stripe s at data_ptrs[s*k + j], recovery block r at rec_ptrs[s*m + r]
+    int table;
+    const uint8_t *const *data_ptrs;
+    const uint8_t *const *rec_ptrs;
+    int8_t *status;               // optional, stripes (at least one of the two outputs is given)
+    uint8_t *bad_rows;            // optional, stripes x m
+    const uint8_t *zero;          // device zeros, at least stripes * m bytes (stripes without bad_rows)
+    const uint8_t *G;             // m x k generator (row 0 = ones); unused when `flat`
+    int k, m, bytes, stripes;
+    int flat;                     // m == 1 or k == 1: every coefficient is 1, lanes over the block's bytes
+    int span, nch, tiles;        // set by launch_verify: as UpdateArgs, and the row tiles of the grid
+};
+
 // Launch trace (codec.cpp): every launch site records the kernel it enqueued, so the
 // calling thread can ask which kernels its last batch call ran (cauchy_256_last_launch).
 void note_launch(const char *kernel);
@@ -227,5 +249,6 @@ hipError_t launch_scatter(const ScatterArgs &a, hipStream_t st);
 hipError_t launch_plan(const PlanArgs &a, hipStream_t st);
 hipError_t launch_ptr_copy(const PtrCopyArgs &a, hipStream_t st);
 hipError_t launch_update(const UpdateArgs &a, hipStream_t st);
+hipError_t launch_verify(const VerifyArgs &a, hipStream_t st);
 
 }  // namespace lh
