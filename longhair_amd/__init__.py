@@ -8,8 +8,9 @@ Python view of the C-ABI library `liblonghair_amd.so` (built from longhair_amd/c
   `cauchy_256_decode(k, m, blocks, block_bytes)` and the `Block` structure, taking the same
   arguments as the C functions (ctypes pointers / arrays) and returning the same codes;
 * batched device-resident helpers on torch uint8 tensors: `encode_batch`, `decode_batch`,
-  `update_batch`, which patches the recovery blocks after a few data blocks changed, and
-  `verify_batch`, which tells whether stored recovery blocks still belong to the stored data.
+  `update_batch`, which patches the recovery blocks after a few data blocks changed,
+  `verify_batch`, which tells whether stored recovery blocks still belong to the stored data, and
+  `reconstruct_batch`, which rebuilds chosen rows (data or recovery) from k survivors out of place.
 
 There is no CPU implementation: importing works without a GPU, but every codec call
 goes through the HIP library and fails loudly (LonghairError / non-zero codes) when no
@@ -310,6 +311,77 @@ def verify_batch_ptrs(k, m, block_bytes, data_ptrs, recovery_ptrs, status=None, 
                                             rows_p, ctypes.c_void_p(_stream_handle(stream)))
     if rc != 0:
         raise LonghairError(rc, "cauchy_256_verify_batch_ptrs")
+    return status
+
+
+def _reconstruct_rows(rows, want_rows, stripes, k, status, device):
+    import torch
+    _cuda_tensor(rows, torch.uint8, "rows", (stripes, k), True, device)
+    _cuda_tensor(want_rows, torch.uint8, "want_rows", None, True, device)
+    _require(want_rows.dim() == 2 and want_rows.shape[0] == stripes, f"want_rows must be [{stripes}, want]")
+    if status is None:
+        status = torch.empty((stripes,), dtype=torch.int8, device=device)
+    _cuda_tensor(status, torch.int8, "status", (stripes,), True, device)
+    return want_rows.shape[1], status
+
+
+def reconstruct_batch(blocks, rows, m, want_rows, out=None, status=None, stream=None):
+    """Rebuild chosen rows of each stripe's codeword from its k survivors, out of place
+    (cauchy_256_reconstruct_batch): the repair after one node, and with it one block per stripe, is lost.
+
+    blocks:    uint8 CUDA tensor [stripes, k, block_bytes] -- the k surviving blocks of each stripe
+               in array order (the reference's Block[] order); only read;
+    rows:      uint8 CUDA tensor [stripes, k] -- each slot's Block.row; only read (decode_batch
+               rewrites its rows, this call does not);
+    want_rows: uint8 CUDA tensor [stripes, want] -- the rows wanted, data (< k) or recovery
+               (k + r), 0xFF = nothing wanted in this entry; a row may repeat or be a survivor;
+    out:       uint8 CUDA tensor [stripes, want, block_bytes]; allocated zero-filled if not given,
+               so a skipped entry reads as zeros.  Must not overlap the inputs.
+    Returns (out, status): status int8 [stripes], 0 ok / -1 invalid survivor rows or a wanted row
+    in [k + m, 0xFE]: that stripe's out blocks are not written."""
+    import torch
+    _block_tensor(blocks, "blocks")
+    stripes, k, nbytes = blocks.shape
+    want, status = _reconstruct_rows(rows, want_rows, stripes, k, status, blocks.device)
+    if out is None:
+        out = torch.zeros((stripes, want, nbytes), dtype=torch.uint8, device=blocks.device)
+    _block_tensor(out, "out")
+    _require(tuple(out.shape) == (stripes, want, nbytes), f"out must be [{stripes}, {want}, {nbytes}]")
+    _require(out.device == blocks.device, "out must be on blocks' device")
+    rc = lib().cauchy_256_reconstruct_batch(k, m, nbytes, stripes, ctypes.c_void_p(blocks.data_ptr()),
+                                            ctypes.c_longlong(blocks.stride(0)), ctypes.c_void_p(rows.data_ptr()), want,
+                                            ctypes.c_void_p(want_rows.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                                            ctypes.c_longlong(out.stride(0)), ctypes.c_void_p(status.data_ptr()),
+                                            ctypes.c_void_p(_stream_handle(stream)))
+    if rc != 0:
+        raise LonghairError(rc, "cauchy_256_reconstruct_batch")
+    return out, status
+
+
+def reconstruct_batch_ptrs(k, m, block_bytes, block_ptrs, rows, want_rows, out_ptrs, status=None, stream=None):
+    """reconstruct_batch for blocks that sit anywhere in device memory
+    (cauchy_256_reconstruct_batch_ptrs).
+
+    block_ptrs: int64 CUDA tensor [stripes, k] of device addresses (Block.data of each slot);
+    rows:       uint8 CUDA tensor [stripes, k];
+    want_rows:  uint8 CUDA tensor [stripes, want];
+    out_ptrs:   int64 CUDA tensor [stripes, want], where each wanted row goes (the entries of 0xFF
+                rows are not read).
+    Returns `status` (int8 [stripes])."""
+    import torch
+    _cuda_tensor(block_ptrs, torch.int64, "block_ptrs")
+    _require(block_ptrs.dim() == 2, "block_ptrs must be [stripes, k]")
+    stripes = block_ptrs.shape[0]
+    blocks_t = _ptr_table(block_ptrs, stripes, k, "block_ptrs")
+    want, status = _reconstruct_rows(rows, want_rows, stripes, k, status, block_ptrs.device)
+    out_t = _ptr_table(out_ptrs, stripes, want, "out_ptrs")
+    _require(out_ptrs.device == block_ptrs.device, "out_ptrs must be on block_ptrs' device")
+    rc = lib().cauchy_256_reconstruct_batch_ptrs(k, m, block_bytes, stripes, blocks_t, ctypes.c_void_p(rows.data_ptr()),
+                                                 want, ctypes.c_void_p(want_rows.data_ptr()), out_t,
+                                                 ctypes.c_void_p(status.data_ptr()),
+                                                 ctypes.c_void_p(_stream_handle(stream)))
+    if rc != 0:
+        raise LonghairError(rc, "cauchy_256_reconstruct_batch_ptrs")
     return status
 
 

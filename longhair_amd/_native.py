@@ -80,12 +80,24 @@ VERIFY_EXPORTS = {
                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                     ctypes.c_void_p, ctypes.c_void_p]),
 }
+# Every symbol include/cauchy_256_reconstruct.h declares (the repair), in both libraries.
+RECONSTRUCT_EXPORTS = {
+    "cauchy_256_reconstruct_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                    ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int,
+                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
+                                                    ctypes.c_void_p, ctypes.c_void_p]),
+    "cauchy_256_reconstruct_batch_ptrs": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                         ctypes.c_void_p]),
+}
 
 
 def bind(l):
-    """Set the ctypes signatures of a loaded copy of the library (every EXPORTS, UPDATE_EXPORTS
-    and VERIFY_EXPORTS symbol must exist; OPTIONAL_EXPORTS where present)."""
-    for name, (res, args) in list(EXPORTS.items()) + list(UPDATE_EXPORTS.items()) + list(VERIFY_EXPORTS.items()):
+    """Set the ctypes signatures of a loaded copy of the library (every EXPORTS, UPDATE_EXPORTS,
+    VERIFY_EXPORTS and RECONSTRUCT_EXPORTS symbol must exist; OPTIONAL_EXPORTS where present)."""
+    for name, (res, args) in (list(EXPORTS.items()) + list(UPDATE_EXPORTS.items()) + list(VERIFY_EXPORTS.items())
+                              + list(RECONSTRUCT_EXPORTS.items())):
         f = getattr(l, name)
         f.restype = res
         f.argtypes = args

@@ -22,6 +22,7 @@
 #include "../../include/cauchy_256_batch.h"
 #include "../../include/cauchy_256_update.h"
 #include "../../include/cauchy_256_verify.h"
+#include "../../include/cauchy_256_reconstruct.h"
 #include "field.hpp"
 #include "jit.hpp"
 #include "host_codec.hpp"
@@ -1017,6 +1018,59 @@ static int verify_batch(int k, int m, int bytes, int stripes, VerifyArgs a, hipS
     return kOk;
 }
 
+// ------------------------------------------------------------------ repair
+// cauchy_256_reconstruct_batch / _ptrs (include/cauchy_256_reconstruct.h): the planner on a copy of
+// the rows (the planners rewrite them; the caller's stay), lh_reconstruct_coef_kernel, then
+// lh_reconstruct_kernel.  Every check comes before the device, so it holds without one.  The
+// stream's workspace holds the plans and, in `work`, the rows' copy, valid[stripes] and the
+// stripes * want * k coefficient bytes, so a captured call never allocates (workspace()).
+static int reconstruct_batch(int k, int m, int bytes, int stripes, int want, const uint8_t *d_rows,
+                             const uint8_t *d_want_rows, ReconstructArgs a, hipStream_t st) {
+    if (k < 1 || k > 256 || m < 1 || m > 256) return fail(kInvalid, "invalid k or m (1..256)");
+    if (bytes <= 0 || stripes < 0 || want < 1) return fail(kInvalid, "invalid block_bytes, stripes or want");
+    if (k + m > 255) return fail(kInvalid, "k + m > 255 (a row is one byte, 0xFF reserved)");
+    if ((long long)want * k > 0x7FFFFFFF) return fail(kInvalid, "want * k > 2^31 - 1 (a stripe's coefficients are indexed by an int)");
+    if (m > 1 && k > 1 && bytes % 8 != 0) return fail(kInvalid, "block_bytes % 8 != 0");
+    const bool table = a.table != 0;
+    if (!table) {
+        if (a.blocks_stride < (long long)k * bytes) return fail(kInvalid, "blocks stride smaller than the stripe");
+        if (a.out_stride < (long long)want * bytes) return fail(kInvalid, "out stride smaller than the wanted blocks");
+    }
+    if (stripes > 0 && (!(table ? (const void *)a.block_ptrs : (const void *)a.blocks) || !d_rows || !d_want_rows ||
+                        !(table ? (const void *)a.out_ptrs : (const void *)a.out)))
+        return fail(kInvalid, "null blocks, rows, want_rows or out argument");
+    if (stripes == 0) return kOk;
+    Device *d = nullptr;
+    if (int rc = current_device(&d)) return rc;
+    a.rows = d_rows;
+    a.want_rows = d_want_rows;
+    a.k = k;
+    a.m = m;
+    a.want = want;
+    a.bytes = bytes;
+    a.stripes = stripes;
+    a.flat = (m == 1 || k == 1) ? 1 : 0;  // every coefficient is 0 or 1: no plan
+    a.gf_exp = d->gf_exp;
+    a.gf_log = d->gf_log;
+    const int e_max = k < m ? k : m;
+    const size_t rows_bytes = ((size_t)stripes * k + 15) & ~(size_t)15, valid_bytes = ((size_t)stripes + 15) & ~(size_t)15;
+    const size_t work_bytes = rows_bytes + valid_bytes + (size_t)stripes * want * k;
+    const size_t plan_bytes = a.flat ? 16 : plan_workspace_bytes(k, m, e_max, stripes);
+    Workspace *w = nullptr;
+    if (int rc = workspace(d, st, plan_bytes, work_bytes, &w)) return rc;
+    if (!a.flat) {
+        if (int rc = device_generator(d, k, m, &a.G, nullptr, st)) return rc;
+        LH_HIP(hipMemcpyAsync(w->work.ptr, d_rows, (size_t)stripes * k, hipMemcpyDeviceToDevice, st));
+        if (int rc = run_planner(d, st, k, m, e_max, stripes, w->work.ptr, nullptr, work_bytes, true, &w)) return rc;
+        a.plan = w->plan.ptr;
+        a.plan_stride = PlanView::bytes(k, m, e_max);
+    }
+    a.valid = w->work.ptr + rows_bytes;
+    a.coef = a.valid + valid_bytes;
+    LH_HIP(launch_reconstruct(a, st));  // (a batch of more than 2^31 - 1 workgroups: hipErrorInvalidValue)
+    return kOk;
+}
+
 // -------------------------------------------------------------- drop-in helpers
 // Where a drop-in block lives: host memory (pageable or pinned), memory the current device's
 // kernels may address directly (its own allocations; managed memory), or another device's
@@ -1631,6 +1685,36 @@ LH_API int cauchy_256_verify_batch_ptrs(int k, int m, int block_bytes, int strip
         a.bad_rows = d_bad_rows;
         a.table = 1;
         return lh::verify_batch(k, m, block_bytes, stripes, a, (hipStream_t)stream);
+    LH_CATCH
+}
+
+LH_API int cauchy_256_reconstruct_batch(int k, int m, int block_bytes, int stripes, const void *d_blocks,
+                                        long long blocks_stride, const unsigned char *d_rows, int want,
+                                        const unsigned char *d_want_rows, void *d_out, long long out_stride,
+                                        signed char *d_status, void *stream) {
+    LH_TRY
+        lh::LaunchTrace trace;
+        lh::ReconstructArgs a{};
+        a.blocks = (const uint8_t *)d_blocks;
+        a.blocks_stride = blocks_stride;
+        a.out = (uint8_t *)d_out;
+        a.out_stride = out_stride;
+        a.status = (int8_t *)d_status;
+        return lh::reconstruct_batch(k, m, block_bytes, stripes, want, d_rows, d_want_rows, a, (hipStream_t)stream);
+    LH_CATCH
+}
+
+LH_API int cauchy_256_reconstruct_batch_ptrs(int k, int m, int block_bytes, int stripes, const void *const *d_block_ptrs,
+                                             const unsigned char *d_rows, int want, const unsigned char *d_want_rows,
+                                             void *const *d_out_ptrs, signed char *d_status, void *stream) {
+    LH_TRY
+        lh::LaunchTrace trace;
+        lh::ReconstructArgs a{};
+        a.block_ptrs = (const uint8_t *const *)d_block_ptrs;
+        a.out_ptrs = (uint8_t *const *)d_out_ptrs;
+        a.status = (int8_t *)d_status;
+        a.table = 1;
+        return lh::reconstruct_batch(k, m, block_bytes, stripes, want, d_rows, d_want_rows, a, (hipStream_t)stream);
     LH_CATCH
 }
 

@@ -18,6 +18,10 @@
 //   lh_verify_kernel        recovery scrub (cauchy_256_verify_batch): is recovery_r ^ sum_j
 //                           B(G[r][j]) data_j zero for every row of a stripe?  The update's
 //                           multiply with a wave-uniform coefficient, nothing stored but flags.
+//   lh_reconstruct_kernel   repair (cauchy_256_reconstruct_batch): wanted rows of the codeword, data
+//                           or recovery, from the k survivors and out of place, out_j = sum_slot
+//                           B(C[j][slot]) block_slot; lh_reconstruct_coef_kernel composes C from
+//                           the planner's single-pass coefficients and validates the stripe.
 //   lh_scatter_kernel       moves recovered blocks from the workspace into their slots.
 //   lh_inverse_gt_kernel    large-m decode phase B (after the windowed phase A left V_r in
 //                           the recovery slots): D_E = A^-1 V by a computed jump into 256
@@ -591,6 +595,209 @@ __global__ void __launch_bounds__(256) lh_verify_kernel(lh::VerifyArgs a) {
         return;
     }
     lh_verify_lane<kUpdateLane, PTR>(a, s, c, tile * TO, min(TO, a.m - tile * TO));
+}
+
+// ------------------------------------------------------------------ repair
+// cauchy_256_reconstruct_batch: the wanted rows of a stripe's codeword from its k survivors, out of
+// place.  Every row is a GF(256)-linear combination of the survivor slots, out_j = sum_slot
+// B(C[j][slot]) block_slot; the planner (on a copy of the rows, want_w) has the combination of the
+// erased originals E_i, w[i][slot], and lh_reconstruct_coef_kernel composes C from it:
+//     wanted row present in slot i0     C[j] = e_{i0}                     (a copy)
+//     wanted row = erased original E_i  C[j] = w[i]
+//     wanted row = absent recovery r    C[j][slot] = [rows[slot] < k] G[r][rows[slot]]
+//                                                    ^ sum_i G[r][E_i] w[i][slot]
+//     m == 1, k == 1 (`flat`)           present: e_{i0}; absent: all ones
+//  * lh_reconstruct_coef_kernel, a wave per stripe: validates the caller's rows itself for every m
+//    (the planner lets m == 1 pass) and the wanted rows, writes status[s] and valid[s], and for a
+//    valid stripe its want x k coefficient bytes (zeros for a 0xFF entry).
+//  * lh_reconstruct_kernel: the lanes, loads and stores of lh_update_kernel (flat over (stripe,
+//    8-byte column of each sub-block), the last lane's window, a span under a lane piecewise; see
+//    there why lanes are 8 bytes, not 16) and the column pipeline of lh_verify_kernel.  Lanes of
+//    one wave belong to different stripes, so the coefficient is a per-lane byte and the multiply
+//    the masked form -- unless a stripe is whole waves (lanes per stripe % 64 == 0, blocks of 4
+//    KiB and multiples): then it is wave-uniform, a scalar, and a zero bit a branch, as in
+//    lh_verify_kernel.  Accumulators start at zero; every out byte is stored by exactly one lane;
+//    a 0xFF entry and a stripe with valid[s] == 0 store nothing (the out pointer of a 0xFF entry
+//    is not read).  Wanted rows in tiles of kGenericTileOut, the tiles placed on the grid as
+//    lh_verify_kernel places its row tiles (measured against the loop in the lane:
+//    profiles/reconstruct_variants.txt); the flat form loops over them.
+//  * `flat`: 16-byte lanes over the whole block, coefficients 0 or 1.
+namespace {
+
+// 4 stripes per workgroup, one wave each; no wave leaves before the last barrier.
+__global__ void __launch_bounds__(256) lh_reconstruct_coef_kernel(lh::ReconstructArgs a) {
+    __shared__ uint8_t gexp[512];
+    __shared__ int16_t glog[256];
+    __shared__ uint8_t slot_of_[4][256];  // row -> slot, 0xFF absent
+    __shared__ uint8_t eidx_[4][256];     // erased original -> its index i (E_i ascending)
+    __shared__ uint8_t erased_[4][128];   // E_i
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    uint8_t *slot_of = slot_of_[wv], *eidx = eidx_[wv], *erased = erased_[wv];
+    gexp[tid] = a.gf_exp[tid];
+    gexp[tid + 256] = a.gf_exp[tid + 256];
+    glog[tid] = a.gf_log[tid];
+    for (int i = lane; i < 256; i += 64) slot_of[i] = 0xFF;
+    const long long s = (long long)blockIdx.x * 4 + wv;
+    const bool live = s < a.stripes;
+    const int k = a.k, m = a.m, n = k + m, want = a.want;
+    const uint8_t *rows = a.rows + (live ? s : 0) * k;
+    const uint8_t *wr = a.want_rows + (live ? s : 0) * want;
+    __syncthreads();
+    bool bad = false;
+    for (int i = lane; i < k; i += 64) {
+        const int r = rows[i];
+        if (r >= n) bad = true;
+        else slot_of[r] = (uint8_t)i;
+    }
+    __syncthreads();
+    for (int i = lane; i < k; i += 64) {
+        const int r = rows[i];
+        if (r < n && slot_of[r] != i) bad = true;  // a repeated row
+    }
+    for (int j = lane; j < want; j += 64) {
+        const int w = wr[j];
+        if (w != 0xFF && w >= n) bad = true;
+    }
+    bad = __ballot(bad) != 0;
+    // Erased originals, ascending (as the planner counts them): distinct rows leave as many as
+    // there are recovery rows among the survivors, at most min(k, m) <= 127.
+    int e = 0;
+    if (!bad && !a.flat) {
+        const unsigned long long below = (1ull << lane) - 1;
+        for (int i0 = 0; i0 < k; i0 += 64) {
+            const int i = i0 + lane;
+            const bool miss = i < k && slot_of[i] == 0xFF;
+            const unsigned long long bm = __ballot(miss);
+            if (miss) {
+                const int q = e + __builtin_popcountll(bm & below);
+                erased[q] = (uint8_t)i;
+                eidx[i] = (uint8_t)q;
+            }
+            e += __builtin_popcountll(bm);
+        }
+    }
+    const lh::PlanView pv(a.plan + (live && !a.flat ? s : 0) * a.plan_stride, k, m, k < m ? k : m);
+    if (!bad && !a.flat && (pv.e() != e || pv.p[1] != 0)) bad = true;  // (the plan is of these rows)
+    if (live && lane == 0) {
+        if (a.status) a.status[s] = bad ? -1 : 0;
+        a.valid[s] = bad ? 0 : 1;
+    }
+    __syncthreads();
+    if (!live || bad) return;
+    const uint8_t *W = pv.w_ptr();
+    uint8_t *C = a.coef + s * want * k;
+    for (int q = lane; q < want * k; q += 64) {
+        const int j = q / k, slot = q - j * k;
+        const int w = wr[j];
+        uint32_t v = 0;
+        if (w != 0xFF) {
+            const int at = slot_of[w];
+            if (at != 0xFF) {
+                v = slot == at;
+            } else if (a.flat) {
+                v = 1;
+            } else if (w < k) {
+                v = W[eidx[w] * k + slot];
+            } else {
+                const uint8_t *g = a.G + (long long)(w - k) * k;
+                const int rs = rows[slot];
+                v = rs < k ? g[rs] : 0;
+                for (int i = 0; i < e; ++i) {
+                    const uint32_t x = W[i * k + slot], y = g[erased[i]];
+                    if (x && y) v ^= gexp[glog[x] + glog[y]];
+                }
+            }
+        }
+        C[q] = (uint8_t)v;
+    }
+}
+
+// Wanted rows [i0, i0 + ni) of lane c of stripe s, over NS sub-blocks (8, or 1: flat).  UNI: the
+// wave's lanes belong to one stripe, so the coefficient is a scalar and a zero bit a branch.
+template <int W, int NS, bool PTR, bool UNI>
+__device__ __forceinline__ void lh_reconstruct_lane(const lh::ReconstructArgs &a, long long s, int c, int i0, int ni) {
+    constexpr int TO = lh::kGenericTileOut;
+    const int at = min(c * W, max(a.span - W, 0));  // (the last lane's window ends with the span)
+    const uint8_t *wr = a.want_rows + s * a.want + i0;
+    bool on[TO], any = false;
+#pragma unroll
+    for (int i = 0; i < TO; ++i) {
+        on[i] = i < ni && wr[i] != 0xFF;
+        any |= on[i];
+    }
+    if (!any) return;
+    const uint8_t *cf = a.coef + (s * a.want + i0) * a.k;
+    auto slot = [&](int j) -> const uint8_t * {
+        return PTR ? a.block_ptrs[s * a.k + j] : a.blocks + s * a.blocks_stride + (long long)j * a.bytes;
+    };
+    Word<W> acc[TO][NS];
+#pragma unroll
+    for (int i = 0; i < TO; ++i)
+#pragma unroll
+        for (int y = 0; y < NS; ++y) wzero(acc[i][y]);
+    Word<W> cur[NS];
+    uint32_t e[TO];
+    lh_update_load<W, NS>(cur, slot(0), at, a.span);
+#pragma unroll
+    for (int i = 0; i < TO; ++i) e[i] = on[i] ? cf[i * a.k] : 0;
+    for (int j = 0; j < a.k; ++j) {
+        const int jn = j + 1 < a.k ? j + 1 : j;  // (the last column reloads itself)
+        Word<W> nxt[NS];
+        uint32_t en[TO];
+        lh_update_load<W, NS>(nxt, slot(jn), at, a.span);
+#pragma unroll
+        for (int i = 0; i < TO; ++i) en[i] = on[i] ? cf[i * a.k + jn] : 0;
+        if constexpr (NS == 8) {
+            Word<W> v[15];
+#pragma unroll
+            for (int y = 0; y < 8; ++y) v[y] = cur[y];
+            lh_ladder<W>(v);
+#pragma unroll
+            for (int i = 0; i < TO; ++i)
+                if (i < ni)
+                    lh_mul_acc<W, UNI>(acc[i], v, UNI ? (uint32_t)__builtin_amdgcn_readfirstlane((int)e[i]) : e[i]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < TO; ++i)
+                if (i < ni) wxor_masked(acc[i][0], cur[0], 0u - (e[i] & 1u));
+        }
+#pragma unroll
+        for (int y = 0; y < NS; ++y) cur[y] = nxt[y];
+#pragma unroll
+        for (int i = 0; i < TO; ++i) e[i] = en[i];
+    }
+#pragma unroll
+    for (int i = 0; i < TO; ++i) {
+        if (on[i]) {
+            uint8_t *out = PTR ? a.out_ptrs[s * a.want + i0 + i] : a.out + s * a.out_stride + (long long)(i0 + i) * a.bytes;
+            lh_update_store<W, NS>(out, acc[i], c, a.span);
+        }
+    }
+}
+
+}  // namespace
+
+template <bool PTR>
+__global__ void __launch_bounds__(256) lh_reconstruct_kernel(lh::ReconstructArgs a) {
+    constexpr int TO = lh::kGenericTileOut;
+    long long chunk = blockIdx.x;
+    int tile = 0;
+    if (a.tiles > 1) {  // workgroups b, b + 8, ...: the tiles of chunk (b / (8 tiles)) * 8 + b % 8
+        const long long q = chunk >> 3;
+        tile = (int)(q % a.tiles);
+        chunk = (q / a.tiles) * 8 + (chunk & 7);
+    }
+    const long long t = chunk * 256 + threadIdx.x;
+    const long long s = t / a.nch;
+    if (s >= a.stripes) return;
+    const int c = (int)(t - s * a.nch);
+    if (!a.valid[s]) return;
+    for (int i0 = tile * TO; i0 < a.want; i0 += a.tiles * TO) {
+        const int ni = min(TO, a.want - i0);
+        if (a.flat) lh_reconstruct_lane<16, 1, PTR, false>(a, s, c, i0, ni);
+        else if (a.nch % 64 == 0) lh_reconstruct_lane<kUpdateLane, 8, PTR, true>(a, s, c, i0, ni);  // whole waves per stripe
+        else lh_reconstruct_lane<kUpdateLane, 8, PTR, false>(a, s, c, i0, ni);
+    }
 }
 
 // ------------------------------------------------------------------------ scatter
@@ -1959,6 +2166,34 @@ hipError_t launch_verify(const VerifyArgs &a, hipStream_t st) {
     const bool ptr = a.table != 0;
     hipLaunchKernelGGL(ptr ? lh_verify_kernel<true> : lh_verify_kernel<false>, dim3((unsigned)groups), dim3(256), 0, st, g);
     note_launch(ptr ? "lh_verify_kernel(pointer table)" : "lh_verify_kernel");
+    return hipGetLastError();
+}
+
+hipError_t launch_reconstruct(const ReconstructArgs &a, hipStream_t st) {
+    if (a.k < 1 || a.m < 1 || a.k + a.m > 255 || a.want < 1 || (long long)a.want * a.k > 0x7FFFFFFF || a.bytes < 1 ||
+        (!a.flat && a.bytes % 8 != 0) ||
+        !a.coef || !a.valid || (!a.flat && !a.plan))
+        return hipErrorInvalidValue;
+    if (a.stripes <= 0) return hipSuccess;
+    ReconstructArgs g = a;
+    g.span = a.flat ? a.bytes : a.bytes / 8;
+    const int lane = a.flat ? 16 : kUpdateLane;
+    g.nch = (g.span + lane - 1) / lane;
+    const long long lanes = (long long)a.stripes * g.nch;
+    long long groups = (lanes + 255) / 256;
+    // the wanted-row tiles on the grid, as launch_verify places its row tiles: 18.5 against 20.5 ms
+    // looped in the lane at k128/m32/8192 x 8 192, want 32 (profiles/reconstruct_variants.txt)
+    g.tiles = a.flat ? 1 : (a.want + kGenericTileOut - 1) / kGenericTileOut;
+    if (g.tiles > 1) groups = (groups + 7) / 8 * 8 * g.tiles;
+    if (groups > 0x7FFFFFFF) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lh_reconstruct_coef_kernel, dim3((unsigned)((a.stripes + 3) / 4)), dim3(256), 0, st, g);
+    note_launch("lh_reconstruct_coef_kernel");
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const bool ptr = a.table != 0;
+    hipLaunchKernelGGL(ptr ? lh_reconstruct_kernel<true> : lh_reconstruct_kernel<false>, dim3((unsigned)groups), dim3(256), 0,
+                       st, g);
+    note_launch(ptr ? "lh_reconstruct_kernel(pointer table)" : "lh_reconstruct_kernel");
     return hipGetLastError();
 }
 

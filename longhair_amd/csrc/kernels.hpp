@@ -231,6 +231,37 @@ struct VerifyArgs {
     int span, nch, tiles;        // set by launch_verify: as UpdateArgs, and the row tiles of the grid
 };
 
+// Repair (cauchy_256_reconstruct_batch): out_j = sum_slot B(C[j][slot]) block_slot over the k
+// survivor slots of a stripe, for its `want` wanted rows.  lh_reconstruct_coef_kernel validates
+// the stripe (survivor rows distinct and < k + m, wanted rows < k + m or 0xFF), writes status[s],
+// valid[s] and C[s][want][k] (from the planner's single-pass W, PlanView::w_ptr; all 0 / 1 when
+// `flat`); lh_reconstruct_kernel applies C and stores the wanted out blocks of the valid stripes.
+struct ReconstructArgs {
+    const uint8_t *blocks;        // survivor slot i of stripe s: blocks + s*blocks_stride + i*bytes
+    long long blocks_stride;
+    uint8_t *out;                 // out block j of stripe s: out + s*out_stride + j*bytes
+    long long out_stride;
+    // table != 0: pointer tables (cauchy_256_reconstruct_batch_ptrs; the strided fields unused):
+    // slot i of stripe s at block_ptrs[s*k + i], out block j at out_ptrs[s*want + j] (not read
+    // where the entry is 0xFF)
+    int table;
+    const uint8_t *const *block_ptrs;
+    uint8_t *const *out_ptrs;
+    const uint8_t *rows;          // the caller's rows[s*k + i] (the planner ran on a copy)
+    const uint8_t *want_rows;     // want_rows[s*want + j]
+    int8_t *status;               // optional, stripes
+    const uint8_t *plan;          // PlanView records of the rows' copy (want_w), e_max = min(k, m); unused when `flat`
+    long long plan_stride;
+    uint8_t *coef;                // workspace: C[s][j][slot] at coef[(s*want + j)*k + slot]
+    uint8_t *valid;               // workspace: valid[s] = 1, or 0: the stripe stores nothing
+    const uint8_t *G;             // m x k generator (row 0 = ones); unused when `flat`
+    const uint8_t *gf_exp;        // 512
+    const int16_t *gf_log;        // 256
+    int k, m, want, bytes, stripes;
+    int flat;                     // m == 1 or k == 1: every coefficient is 0 or 1, lanes over the block's bytes
+    int span, nch, tiles;         // set by launch_reconstruct: as UpdateArgs, and the wanted-row tiles of the grid
+};
+
 // Launch trace (codec.cpp): every launch site records the kernel it enqueued, so the
 // calling thread can ask which kernels its last batch call ran (cauchy_256_last_launch).
 void note_launch(const char *kernel);
@@ -250,5 +281,6 @@ hipError_t launch_plan(const PlanArgs &a, hipStream_t st);
 hipError_t launch_ptr_copy(const PtrCopyArgs &a, hipStream_t st);
 hipError_t launch_update(const UpdateArgs &a, hipStream_t st);
 hipError_t launch_verify(const VerifyArgs &a, hipStream_t st);
+hipError_t launch_reconstruct(const ReconstructArgs &a, hipStream_t st);
 
 }  // namespace lh
