@@ -112,7 +112,13 @@ const char *cauchy_256_last_launch(void);
  * wave times the waves of a workgroup, as the launches size their grids; the family form under
  * the LH_FAMILY=1 define); 1 when a stripe fills a wave or more (the windowed kernels
  * included), 0 when no specialised configuration serves the shape.  Like 2 / 5 / 8 / 9 it reads
- * the configuration only and needs no device. */
+ * the configuration only and needs no device.  `what` = 12 (encode) / 13 (decode): the whole
+ * stripes one wave of that kernel covers; 0 when a stripe spans waves (the windowed kernels
+ * included) or no specialised configuration serves the shape.  The register-network kernels
+ * address a wave's stripes through one 32-bit range, so a strided batch runs them only while
+ * stride * max(1, stripes per wave) < 2^31 bytes (the input stride: the data of an encode, the
+ * blocks of a decode); from that stride on the call takes the windowed or generic kernels, which
+ * address in 64 bits, with the same bytes as result.  Pointer-table calls have no such limit. */
 int cauchy_256_batch_path(int k, int m, int block_bytes, int what);
 
 /* Compile the specialised kernels of a shape into the on-disk code-object cache

@@ -528,6 +528,15 @@ def stripes_per_workgroup(k, m, block_bytes, decode=False):
     return lib().cauchy_256_batch_path(k, m, block_bytes, 11 if decode else 10)
 
 
+def stripes_per_wave(k, m, block_bytes, decode=False):
+    """Whole stripes one wave of the shape's strided specialised encode (decode) kernel covers
+    (cauchy_256_batch_path what = 12 / 13; jit.cpp cfg.spw): 0 when a stripe spans waves (the
+    windowed kernels included) or no specialised configuration serves the shape.  A strided batch
+    keeps its register-network kernel while stride * max(1, stripes_per_wave) < 2^31 (codec.cpp
+    route).  Needs no device."""
+    return lib().cauchy_256_batch_path(k, m, block_bytes, 13 if decode else 12)
+
+
 def jump_lanes(k, m, block_bytes, decode=False):
     """Dword lanes per sub-block of the generic jump kernel the library launches for this
     shape on the current device (codec.cpp jump_layout): 1 = lh_apply_jump_kernel, 2 =

@@ -1833,8 +1833,11 @@ LH_API int cauchy_256_batch_path(int k, int m, int block_bytes, int what) {
             return a.dw;
         }
         std::vector<lh::JitConfig> cfgs;  // the strided module of the role: none, windowed or register network
-        lh::shape_configs(k, m, block_bytes, what == 1 || what == 11, lh::kFormStrided, &cfgs);
+        lh::shape_configs(k, m, block_bytes, what == 1 || what == 11 || what == 13, lh::kFormStrided, &cfgs);
         if (cfgs.empty()) return 0;
+        // Stripes per wave of the strided specialised kernel: route()'s range test multiplies the
+        // stride by it (by 1 where a stripe spans waves: 0 here, the windowed kernels included).
+        if (what == 12 || what == 13) return cfgs[0].spw;
         if (what == 10 || what == 11) {
             // Stripes per workgroup of the strided specialised kernel: the stripes of a wave times
             // the waves of a workgroup, as jit_encode_blocks (launch_jit_encode, its family form

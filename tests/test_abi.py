@@ -148,6 +148,45 @@ def test_stripes_per_workgroup(monkeypatch):
     assert [path(10, 4, 64, w) for w in (10, 11)] == [0, 0]
 
 
+def test_stripes_per_wave(monkeypatch):
+    """cauchy_256_batch_path what = 12 / 13: the whole stripes one wave of the strided specialised
+    encode / decode covers (jit.cpp cfg.spw), 0 when a stripe spans waves or nothing is specialised
+    -- route()'s range test multiplies the stride by it, and tests/test_gpu_far.py computes the
+    largest admitted and the first refused stride from it.  For every register-network case of
+    the kernel catalogue (tests/test_gpu_stripe_counts.py) the workgroup figure of what = 10 / 11
+    is this one times the waves of a workgroup (four for the decode)."""
+    import longhair_amd
+    import test_gpu_stripe_counts as sc
+    from test_gpu_far import _is_register
+    path = longhair_amd.lib().cauchy_256_batch_path
+    spw = longhair_amd.stripes_per_wave
+    assert [path(10, 4, 64, w) for w in (12, 13)] == [64, 64]
+    assert [path(29, 4, 1296, w) for w in (12, 13)] == [3, 3]
+    assert [path(8, 3, 8128, w) for w in (12, 13)] == [1, 0]           # decode: two waves per stripe
+    assert [path(40, 13, 2048, 12), path(40, 12, 2048, 13)] == [0, 0]  # the windowed kernels
+    assert [path(9, 9, 64, 13), path(10, 13, 64, 12), path(10, 1, 100, 12), path(1, 3, 40, 13)] == [0, 0, 0, 0]
+    assert spw(29, 4, 1296) == 3 and spw(65, 4, 64, decode=True) == 64
+    checked = 0
+    for decode, cases in ((True, sc.DECODE), (False, sc.ENCODE)):
+        for case in cases:
+            if not _is_register(case):
+                continue
+            with monkeypatch.context() as mp:
+                for key, v in case.env.items():
+                    mp.setenv(key, v)
+                k, m, b = (case.k, case.m, case.nbytes) if case.k is not None else sc._sample_shape(longhair_amd, case.id)
+                T, w = longhair_amd.stripes_per_workgroup(k, m, b, decode), spw(k, m, b, decode)
+                assert T >= 1 and w >= 0, (case.id, T, w)
+                if decode:
+                    assert T == (w * 4 if w else 1), (case.id, T, w)
+                else:
+                    assert (T % w == 0 and 1 <= T // w <= 8) if w else T == 1, (case.id, T, w)
+                checked += 1
+    assert checked == 15
+    monkeypatch.setenv("LONGHAIR_AMD_PATH", "generic")
+    assert [path(10, 4, 64, w) for w in (12, 13)] == [0, 0]
+
+
 def test_lds_staging_policy():
     """jit.cpp jit_config_for: the register networks stage their columns by LDS-DMA for 8-byte
     lanes, whole stripes per wave and 16-byte-multiple blocks, unless a stripe's partial last
