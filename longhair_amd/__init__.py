@@ -9,7 +9,8 @@ Python view of the C-ABI library `liblonghair_amd.so` (built from longhair_amd/c
   arguments as the C functions (ctypes pointers / arrays) and returning the same codes;
 * batched device-resident helpers on torch uint8 tensors: `encode_batch`, `decode_batch`,
   `update_batch`, which patches the recovery blocks after a few data blocks changed,
-  `verify_batch`, which tells whether stored recovery blocks still belong to the stored data, and
+  `verify_batch`, which tells whether stored recovery blocks still belong to the stored data,
+  `locate_batch`, which also names the one corrupt block, data or recovery, of a bad stripe, and
   `reconstruct_batch`, which rebuilds chosen rows (data or recovery) from k survivors out of place.
 
 There is no CPU implementation: importing works without a GPU, but every codec call
@@ -312,6 +313,71 @@ def verify_batch_ptrs(k, m, block_bytes, data_ptrs, recovery_ptrs, status=None, 
     if rc != 0:
         raise LonghairError(rc, "cauchy_256_verify_batch_ptrs")
     return status
+
+
+def _locate_outputs(stripes, status, rows, device):
+    import torch
+    if status is None:
+        status = torch.empty((stripes,), dtype=torch.int8, device=device)
+    _cuda_tensor(status, torch.int8, "status", (stripes,), True, device)
+    if rows is None:
+        rows = torch.empty((stripes,), dtype=torch.uint8, device=device)
+    _cuda_tensor(rows, torch.uint8, "rows", (stripes,), True, device)
+    return status, rows
+
+
+def locate_batch(data, recovery, status=None, rows=None, stream=None):
+    """Scrub stored stripes and name the one corrupt block of a bad stripe
+    (cauchy_256_locate_batch): verify_batch's pass, then a search only in the stripes it flags.
+
+    data:     uint8 CUDA tensor [stripes, k, block_bytes];
+    recovery: uint8 CUDA tensor [stripes, m, block_bytes]; both are only read.
+    Returns (status, rows), int8 [stripes] and uint8 [stripes], allocated if not given:
+      status 0, row 0xFF  the stripe is clean (verify_batch's 0);
+      status 1, row x     replacing block x alone makes the stripe clean: data block x < k, or
+                          recovery block x - k; unique for m >= 2;
+      status 2, row 0xFF  no single block explains the stripe (several corrupt blocks, or m == 1).
+    0xFF is reconstruct_batch's "nothing wanted", so the repair takes the rows as they are:
+
+        status, rows = locate_batch(data, recovery)
+        reconstruct_batch(survivors, survivor_rows, m, rows.unsqueeze(1), out)
+
+    with, per stripe, any k blocks other than the located one as survivors."""
+    _block_tensor(data, "data")
+    _block_tensor(recovery, "recovery")
+    stripes, k, nbytes = data.shape
+    m = recovery.shape[1]
+    _require(tuple(recovery.shape) == (stripes, m, nbytes), f"recovery must be [{stripes}, m, {nbytes}]")
+    _require(recovery.device == data.device, "recovery must be on data's device")
+    status, rows = _locate_outputs(stripes, status, rows, data.device)
+    rc = lib().cauchy_256_locate_batch(k, m, nbytes, stripes, ctypes.c_void_p(data.data_ptr()),
+                                       ctypes.c_longlong(data.stride(0)), ctypes.c_void_p(recovery.data_ptr()),
+                                       ctypes.c_longlong(recovery.stride(0)), ctypes.c_void_p(status.data_ptr()),
+                                       ctypes.c_void_p(rows.data_ptr()), ctypes.c_void_p(_stream_handle(stream)))
+    if rc != 0:
+        raise LonghairError(rc, "cauchy_256_locate_batch")
+    return status, rows
+
+
+def locate_batch_ptrs(k, m, block_bytes, data_ptrs, recovery_ptrs, status=None, rows=None, stream=None):
+    """locate_batch for blocks that sit anywhere in device memory (cauchy_256_locate_batch_ptrs).
+
+    data_ptrs:     int64 CUDA tensor [stripes, k] of device addresses;
+    recovery_ptrs: int64 CUDA tensor [stripes, m].
+    Returns (status, rows) as locate_batch."""
+    import torch
+    _cuda_tensor(data_ptrs, torch.int64, "data_ptrs")
+    _require(data_ptrs.dim() == 2, "data_ptrs must be [stripes, k]")
+    stripes = data_ptrs.shape[0]
+    data_t = _ptr_table(data_ptrs, stripes, k, "data_ptrs")
+    rec_t = _ptr_table(recovery_ptrs, stripes, m, "recovery_ptrs")
+    _require(recovery_ptrs.device == data_ptrs.device, "recovery_ptrs must be on data_ptrs' device")
+    status, rows = _locate_outputs(stripes, status, rows, data_ptrs.device)
+    rc = lib().cauchy_256_locate_batch_ptrs(k, m, block_bytes, stripes, data_t, rec_t, ctypes.c_void_p(status.data_ptr()),
+                                            ctypes.c_void_p(rows.data_ptr()), ctypes.c_void_p(_stream_handle(stream)))
+    if rc != 0:
+        raise LonghairError(rc, "cauchy_256_locate_batch_ptrs")
+    return status, rows
 
 
 def _reconstruct_rows(rows, want_rows, stripes, k, status, device):

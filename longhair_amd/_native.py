@@ -80,6 +80,15 @@ VERIFY_EXPORTS = {
                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                     ctypes.c_void_p, ctypes.c_void_p]),
 }
+# Every symbol include/cauchy_256_locate.h declares (scrub and name the corrupt block), in both libraries.
+LOCATE_EXPORTS = {
+    "cauchy_256_locate_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
+                                               ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "cauchy_256_locate_batch_ptrs": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_void_p]),
+}
 # Every symbol include/cauchy_256_reconstruct.h declares (the repair), in both libraries.
 RECONSTRUCT_EXPORTS = {
     "cauchy_256_reconstruct_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -95,9 +104,10 @@ RECONSTRUCT_EXPORTS = {
 
 def bind(l):
     """Set the ctypes signatures of a loaded copy of the library (every EXPORTS, UPDATE_EXPORTS,
-    VERIFY_EXPORTS and RECONSTRUCT_EXPORTS symbol must exist; OPTIONAL_EXPORTS where present)."""
+    VERIFY_EXPORTS, LOCATE_EXPORTS and RECONSTRUCT_EXPORTS symbol must exist; OPTIONAL_EXPORTS where
+    present)."""
     for name, (res, args) in (list(EXPORTS.items()) + list(UPDATE_EXPORTS.items()) + list(VERIFY_EXPORTS.items())
-                              + list(RECONSTRUCT_EXPORTS.items())):
+                              + list(LOCATE_EXPORTS.items()) + list(RECONSTRUCT_EXPORTS.items())):
         f = getattr(l, name)
         f.restype = res
         f.argtypes = args

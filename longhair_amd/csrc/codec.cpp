@@ -1,5 +1,6 @@
 // codec.cpp -- the C ABI: drop-in cauchy_256.h entry points and the batched
-// device-resident extension (cauchy_256_batch.h, cauchy_256_update.h, cauchy_256_verify.h).
+// device-resident extension (cauchy_256_batch.h, cauchy_256_update.h, cauchy_256_verify.h,
+// cauchy_256_locate.h, cauchy_256_reconstruct.h).
 //
 // Host code only validates parameters, looks up plans/kernels and enqueues work; every
 // byte of encode/decode output is produced by GPU kernels (kernels.hip, jit_codec.hip).
@@ -22,6 +23,7 @@
 #include "../../include/cauchy_256_batch.h"
 #include "../../include/cauchy_256_update.h"
 #include "../../include/cauchy_256_verify.h"
+#include "../../include/cauchy_256_locate.h"
 #include "../../include/cauchy_256_reconstruct.h"
 #include "field.hpp"
 #include "jit.hpp"
@@ -1018,6 +1020,51 @@ static int verify_batch(int k, int m, int bytes, int stripes, VerifyArgs a, hipS
     return kOk;
 }
 
+// ------------------------------------------------------------------ locate
+// cauchy_256_locate_batch / _ptrs (include/cauchy_256_locate.h): the scrub into the stream's
+// workspace, lh_locate_kernel, lh_locate_finish_kernel (launch_locate).  Every check comes before
+// the device, so it holds without one.  The workspace's `work` holds bad_rows[stripes][m] and the
+// stripes vote words; the zero page clears both.  Generator, zero page and workspace are all
+// settled before anything is enqueued, so a captured call that would have to allocate returns
+// with the stream untouched.
+static int locate_batch(int k, int m, int bytes, int stripes, LocateArgs a, hipStream_t st) {
+    if (k < 1 || k > 256 || m < 1 || m > 256) return fail(kInvalid, "invalid k or m (1..256)");
+    if (bytes <= 0 || stripes < 0) return fail(kInvalid, "invalid block_bytes or stripes");
+    if (m > 1 && k > 1 && bytes % 8 != 0) return fail(kInvalid, "block_bytes % 8 != 0");
+    if (m >= 2 && k + m > 255) return fail(kInvalid, "k + m > 255 (a row is one byte, 0xFF reserved)");
+    VerifyArgs &v = a.v;
+    const bool table = v.table != 0;
+    if (!table) {
+        if (v.data_stride < (long long)k * bytes) return fail(kInvalid, "data stride smaller than the stripe");
+        if (v.rec_stride < (long long)m * bytes) return fail(kInvalid, "recovery stride smaller than the stripe");
+    }
+    if (!a.status || !a.rows) return fail(kInvalid, "null status or rows: both outputs are required");
+    if (stripes > 0 && (!(table ? (const void *)v.data_ptrs : (const void *)v.data) ||
+                        !(table ? (const void *)v.rec_ptrs : (const void *)v.rec)))
+        return fail(kInvalid, "null data or recovery argument");
+    if (stripes == 0) return kOk;
+    Device *d = nullptr;
+    if (int rc = current_device(&d)) return rc;
+    v.k = k;
+    v.m = m;
+    v.bytes = bytes;
+    v.stripes = stripes;
+    v.flat = (m == 1 || k == 1) ? 1 : 0;  // every coefficient is 1
+    const size_t bad_bytes = ((size_t)stripes * m + 15) & ~(size_t)15, vote_bytes = (size_t)stripes * sizeof(uint32_t);
+    Workspace *w = nullptr;
+    if (int rc = workspace(d, st, 0, bad_bytes + vote_bytes, &w)) return rc;
+    if (!v.flat)
+        if (int rc = device_generator(d, k, m, &v.G, nullptr, st)) return rc;
+    size_t need = 64;
+    while (need < std::max((size_t)stripes * m, vote_bytes)) need *= 2;
+    if (int rc = zero_page(d, need, &v.zero, st)) return rc;
+    v.status = nullptr;
+    v.bad_rows = w->work.ptr;
+    a.votes = (uint32_t *)(w->work.ptr + bad_bytes);
+    LH_HIP(launch_locate(a, st));  // (a batch of more than 2^31 - 1 workgroups: hipErrorInvalidValue)
+    return kOk;
+}
+
 // ------------------------------------------------------------------ repair
 // cauchy_256_reconstruct_batch / _ptrs (include/cauchy_256_reconstruct.h): the planner on a copy of
 // the rows (the planners rewrite them; the caller's stay), lh_reconstruct_coef_kernel, then
@@ -1685,6 +1732,37 @@ LH_API int cauchy_256_verify_batch_ptrs(int k, int m, int block_bytes, int strip
         a.bad_rows = d_bad_rows;
         a.table = 1;
         return lh::verify_batch(k, m, block_bytes, stripes, a, (hipStream_t)stream);
+    LH_CATCH
+}
+
+LH_API int cauchy_256_locate_batch(int k, int m, int block_bytes, int stripes, const void *d_data, long long data_stride,
+                                   const void *d_recovery, long long recovery_stride, signed char *d_status,
+                                   unsigned char *d_rows, void *stream) {
+    LH_TRY
+        lh::LaunchTrace trace;
+        lh::LocateArgs a{};
+        a.v.data = (const uint8_t *)d_data;
+        a.v.data_stride = data_stride;
+        a.v.rec = (const uint8_t *)d_recovery;
+        a.v.rec_stride = recovery_stride;
+        a.status = (int8_t *)d_status;
+        a.rows = d_rows;
+        return lh::locate_batch(k, m, block_bytes, stripes, a, (hipStream_t)stream);
+    LH_CATCH
+}
+
+LH_API int cauchy_256_locate_batch_ptrs(int k, int m, int block_bytes, int stripes, const void *const *d_data_ptrs,
+                                        const void *const *d_recovery_ptrs, signed char *d_status,
+                                        unsigned char *d_rows, void *stream) {
+    LH_TRY
+        lh::LaunchTrace trace;
+        lh::LocateArgs a{};
+        a.v.data_ptrs = (const uint8_t *const *)d_data_ptrs;
+        a.v.rec_ptrs = (const uint8_t *const *)d_recovery_ptrs;
+        a.v.table = 1;
+        a.status = (int8_t *)d_status;
+        a.rows = d_rows;
+        return lh::locate_batch(k, m, block_bytes, stripes, a, (hipStream_t)stream);
     LH_CATCH
 }
 

@@ -18,6 +18,10 @@
 //   lh_verify_kernel        recovery scrub (cauchy_256_verify_batch): is recovery_r ^ sum_j
 //                           B(G[r][j]) data_j zero for every row of a stripe?  The update's
 //                           multiply with a wave-uniform coefficient, nothing stored but flags.
+//   lh_locate_kernel        after the scrub (cauchy_256_locate_batch): for a stripe whose rows are
+//                           all bad, the one data column j with s_r == B(G[r][j]) s_0 for every row,
+//                           found per lane and merged per stripe by a vote;
+//                           lh_locate_finish_kernel writes the stripe's status and row.
 //   lh_reconstruct_kernel   repair (cauchy_256_reconstruct_batch): wanted rows of the codeword, data
 //                           or recovery, from the k survivors and out of place, out_j = sum_slot
 //                           B(C[j][slot]) block_slot; lh_reconstruct_coef_kernel composes C from
@@ -595,6 +599,205 @@ __global__ void __launch_bounds__(256) lh_verify_kernel(lh::VerifyArgs a) {
         return;
     }
     lh_verify_lane<kUpdateLane, PTR>(a, s, c, tile * TO, min(TO, a.m - tile * TO));
+}
+
+// ------------------------------------------------------------------ locate
+// cauchy_256_locate_batch: which single block explains a bad stripe (include/cauchy_256_locate.h).
+// lh_verify_kernel has written the stripe's bad rows; what they decide alone (none bad, one bad
+// row = that recovery block, m == 1 or 2 .. m - 1 bad rows = no single block) is left to
+// lh_locate_finish_kernel.  lh_locate_kernel works on the stripes whose m >= 2 rows are all bad: a
+// corrupt data block x shows as s_r == B(G[r][x]) s_0 for every row r (row 0 of G is ones, so s_0
+// is the error itself).
+//  * The scrub's lanes (8-byte columns of the 8 sub-blocks, the last lane's window, a span under a
+//    lane piecewise; `flat` 16-byte lanes for k == 1), one plain grid, no row tiles on the grid: a
+//    lane leaves at the first row of its stripe that is not bad, so a clean batch costs a byte read
+//    per lane.
+//  * A lane recomputes the syndromes of the first row tile.  With s_0 != 0 it looks for the column
+//    of row 1: B(G[1][j]) s_0 == s_1 over the whole window.  The candidate j is the loop index, the
+//    same for every lane still looking, so the coefficient is a scalar and the multiply the
+//    branching form.  The entries of a row of G are distinct and a window with s_0 != 0 has an
+//    element u != 0 with (g ^ g') u != 0, so at most one column matches: the first match is it.
+//  * Then every row tile is checked against B(G[r][j]) s_0, j the lane's own column (lanes of one
+//    wave belong to different stripes when blocks are small): the masked multiply.  With s_0 == 0
+//    the expectation is zero whatever the column, which is the case "every s_r must be zero".
+//  * A lane whose syndromes are all zero says nothing.  Every other lane votes: its column, or
+//    kLocateConflict when no column matched or a row failed.  votes[s] (cleared to 0 by the
+//    launcher) takes the first column by a compare-and-swap from 0; a lane that finds another
+//    value than its own there, or has a conflict to report, ORs kLocateConflict in, which absorbs.
+//    After the first successful swap the word only ever holds that column or the conflict, so
+//    every lane with another column sees a mismatch whenever it arrives, and the final word is the
+//    common column iff all voters agreed on one: it does not depend on the order of the lanes.
+namespace {
+
+// acc[i] = the syndrome of row i0 + i, i < ni, in the lane's window `at` of stripe s: the column
+// pipeline of lh_verify_lane.  (A copy: with the loop shared, lh_verify_kernel compiled to other,
+// longer code, and the scrub is to stay as it was measured.)
+template <int W, bool PTR>
+__device__ __forceinline__ void lh_syndromes(const lh::VerifyArgs &a, long long s, int at, int i0, int ni,
+                                             Word<W> (&acc)[lh::kGenericTileOut][8]) {
+    constexpr int TO = lh::kGenericTileOut;
+#pragma unroll
+    for (int i = 0; i < TO; ++i)
+        if (i < ni) lh_update_load<W, 8>(acc[i], lh_verify_rec<PTR>(a, s, i0 + i), at, a.span);
+    const uint8_t *g = a.G + (long long)i0 * a.k;
+    Word<W> cur[8];
+    uint32_t e[TO];
+    lh_update_load<W, 8>(cur, lh_verify_data<PTR>(a, s, 0), at, a.span);
+#pragma unroll
+    for (int i = 0; i < TO; ++i) e[i] = i < ni ? g[i * a.k] : 0;
+    for (int j = 0; j < a.k; ++j) {
+        const int jn = j + 1 < a.k ? j + 1 : j;  // (the last column reloads itself)
+        Word<W> nxt[8];
+        uint32_t en[TO];
+        lh_update_load<W, 8>(nxt, lh_verify_data<PTR>(a, s, jn), at, a.span);
+#pragma unroll
+        for (int i = 0; i < TO; ++i) en[i] = i < ni ? g[i * a.k + jn] : 0;
+        Word<W> v[15];
+#pragma unroll
+        for (int y = 0; y < 8; ++y) v[y] = cur[y];
+        lh_ladder<W>(v);
+#pragma unroll
+        for (int i = 0; i < TO; ++i)
+            if (i < ni)
+                lh_mul_acc<W, true>(acc[i], v, (uint32_t)__builtin_amdgcn_readfirstlane((int)e[i]));
+#pragma unroll
+        for (int y = 0; y < 8; ++y) cur[y] = nxt[y];
+#pragma unroll
+        for (int i = 0; i < TO; ++i) e[i] = en[i];
+    }
+}
+
+// The OR of a column's words: non-zero iff any bit of the lane's window is set.
+template <int W>
+__device__ __forceinline__ uint32_t lh_any(const Word<W> (&d)[8]) {
+    uint32_t any = 0;
+#pragma unroll
+    for (int y = 0; y < 8; ++y)
+#pragma unroll
+        for (int w = 0; w < Word<W>::N; ++w) any |= d[y].v[w];
+    return any;
+}
+
+template <int W, bool PTR>
+__device__ __forceinline__ uint32_t lh_locate_lane(const lh::VerifyArgs &a, long long s, int c) {
+    constexpr int TO = lh::kGenericTileOut;
+    const int at = min(c * W, max(a.span - W, 0));  // (the last lane's window ends with the span)
+    Word<W> acc[TO][8];
+    int ni = min(TO, a.m);
+    lh_syndromes<W, PTR>(a, s, at, 0, ni, acc);
+    Word<W> v0[15];
+#pragma unroll
+    for (int y = 0; y < 8; ++y) v0[y] = acc[0][y];
+    lh_ladder<W>(v0);
+    const bool some0 = lh_any<W>(acc[0]) != 0;
+    int col = -1;
+    if (some0) {
+        const uint8_t *g1 = a.G + a.k;
+        for (int j = 0; j < a.k; ++j) {
+            Word<W> t[8];
+#pragma unroll
+            for (int y = 0; y < 8; ++y) t[y] = acc[1][y];
+            lh_mul_acc<W, true>(t, v0, (uint32_t)__builtin_amdgcn_readfirstlane((int)g1[j]));
+            if (!lh_any<W>(t)) {
+                col = j;
+                break;
+            }
+        }
+    }
+    const int cj = col < 0 ? 0 : col;
+    uint32_t some = 0, diff = 0;
+    for (int i0 = 0;;) {
+#pragma unroll
+        for (int i = 0; i < TO; ++i) {
+            if (i < ni) {
+                some |= lh_any<W>(acc[i]);
+                lh_mul_acc<W, false>(acc[i], v0, a.G[(long long)(i0 + i) * a.k + cj]);
+                diff |= lh_any<W>(acc[i]);
+            }
+        }
+        i0 += TO;
+        if (i0 >= a.m) break;
+        ni = min(TO, a.m - i0);
+        lh_syndromes<W, PTR>(a, s, at, i0, ni, acc);
+    }
+    if (!some) return 0;
+    return (some0 && col < 0) || diff ? lh::kLocateConflict : (uint32_t)col + 1;
+}
+
+// k == 1, m >= 2: the recovery blocks are copies of the data block, every s_r = recovery_r ^ data.
+template <bool PTR>
+__device__ __forceinline__ uint32_t lh_locate_flat(const lh::VerifyArgs &a, long long s, int c) {
+    constexpr int W = 16;
+    const int at = min(c * W, max(a.span - W, 0));
+    Word<W> d[1], r[1], s0;
+    lh_update_load<W, 1>(d, lh_verify_data<PTR>(a, s, 0), at, a.span);
+    uint32_t some = 0, diff = 0;
+    wzero(s0);
+    for (int i = 0; i < a.m; ++i) {
+        lh_update_load<W, 1>(r, lh_verify_rec<PTR>(a, s, i), at, a.span);
+        wxor(r[0], d[0]);
+        if (i == 0) s0 = r[0];
+#pragma unroll
+        for (int w = 0; w < Word<W>::N; ++w) {
+            some |= r[0].v[w];
+            diff |= r[0].v[w] ^ s0.v[w];
+        }
+    }
+    if (!some) return 0;
+    return diff ? lh::kLocateConflict : 1u;
+}
+
+}  // namespace
+
+template <bool PTR>
+__global__ void __launch_bounds__(256) lh_locate_kernel(lh::LocateArgs a) {
+    const lh::VerifyArgs &v = a.v;
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long s = t / v.nch;
+    if (s >= v.stripes) return;
+    const int c = (int)(t - s * v.nch);
+    const uint8_t *bad = v.bad_rows + s * v.m;
+    for (int r = 0; r < v.m; ++r)
+        if (!bad[r]) return;  // not every row is bad: the finishing kernel has the answer
+    const uint32_t vote = v.flat ? lh_locate_flat<PTR>(v, s, c) : lh_locate_lane<kUpdateLane, PTR>(v, s, c);
+    if (!vote) return;
+    uint32_t *word = a.votes + s;
+    if (vote != lh::kLocateConflict) {
+        const uint32_t old = atomicCAS(word, 0u, vote);
+        if (old == 0u || old == vote) return;
+    }
+    atomicOr(word, lh::kLocateConflict);
+}
+
+// A thread per stripe: the two output bytes from the stripe's bad rows and, where all m >= 2 rows
+// are bad, the lanes' vote.  The only writer of status and rows.
+__global__ void __launch_bounds__(256) lh_locate_finish_kernel(lh::LocateArgs a) {
+    const lh::VerifyArgs &v = a.v;
+    const long long s = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (s >= v.stripes) return;
+    const uint8_t *bad = v.bad_rows + s * v.m;
+    int n = 0, first = 0;
+    for (int r = 0; r < v.m; ++r) {
+        if (bad[r]) {
+            if (!n) first = r;
+            ++n;
+        }
+    }
+    int status = 2, row = 0xFF;
+    if (n == 0) {
+        status = 0;
+    } else if (v.m >= 2 && n == 1) {
+        status = 1;
+        row = v.k + first;
+    } else if (v.m >= 2 && n == v.m) {
+        const uint32_t vote = a.votes[s];
+        if (vote >= 1u && vote <= (uint32_t)v.k) {
+            status = 1;
+            row = (int)vote - 1;
+        }
+    }
+    a.status[s] = (int8_t)status;
+    a.rows[s] = (uint8_t)row;
 }
 
 // ------------------------------------------------------------------ repair
@@ -2166,6 +2369,33 @@ hipError_t launch_verify(const VerifyArgs &a, hipStream_t st) {
     const bool ptr = a.table != 0;
     hipLaunchKernelGGL(ptr ? lh_verify_kernel<true> : lh_verify_kernel<false>, dim3((unsigned)groups), dim3(256), 0, st, g);
     note_launch(ptr ? "lh_verify_kernel(pointer table)" : "lh_verify_kernel");
+    return hipGetLastError();
+}
+
+hipError_t launch_locate(const LocateArgs &a, hipStream_t st) {
+    if (!a.votes || !a.status || !a.rows || !a.v.bad_rows || a.v.status || a.v.k < 1 || a.v.m < 1 ||
+        (a.v.m >= 2 && a.v.k + a.v.m > 255))
+        return hipErrorInvalidValue;
+    if (a.v.stripes <= 0) return hipSuccess;
+    hipError_t e = launch_verify(a.v, st);  // (checks the rest of the shape; clears bad_rows first)
+    if (e != hipSuccess) return e;
+    LocateArgs g = a;
+    g.v.span = a.v.flat ? a.v.bytes : a.v.bytes / 8;
+    g.v.nch = (g.v.span + (a.v.flat ? 16 : kUpdateLane) - 1) / (a.v.flat ? 16 : kUpdateLane);
+    g.v.tiles = 1;
+    const bool ptr = a.v.table != 0;
+    if (a.v.m >= 2) {  // (m == 1: nothing to search, the finishing kernel does not read the votes)
+        const long long groups = ((long long)a.v.stripes * g.v.nch + 255) / 256;  // (launch_verify checked the range)
+        // the votes start from zero by a copy from the zero page, as launch_verify clears its outputs
+        e = hipMemcpyAsync(a.votes, a.v.zero, (size_t)a.v.stripes * sizeof(uint32_t), hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(ptr ? lh_locate_kernel<true> : lh_locate_kernel<false>, dim3((unsigned)groups), dim3(256), 0, st, g);
+        note_launch(ptr ? "lh_locate_kernel(pointer table)" : "lh_locate_kernel");
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(lh_locate_finish_kernel, dim3((unsigned)((a.v.stripes + 255) / 256)), dim3(256), 0, st, g);
+    note_launch("lh_locate_finish_kernel");
     return hipGetLastError();
 }
 

@@ -231,6 +231,21 @@ struct VerifyArgs {
     int span, nch, tiles;        // set by launch_verify: as UpdateArgs, and the row tiles of the grid
 };
 
+// Locate (cauchy_256_locate_batch): the scrub of `v` into the workspace's bad_rows (v.status NULL,
+// v.bad_rows [stripes][m]), then lh_locate_kernel over the same lanes for the stripes whose m rows
+// are all bad -- each lane with a non-zero syndrome votes for the one data column that explains it,
+// or for "none", into votes[s] -- then lh_locate_finish_kernel, a thread per stripe, which writes
+// the two output bytes from the stripe's bad rows and its vote.
+// votes[s]: 0 no vote yet (cleared from the zero page), j + 1 every vote so far is column j,
+// kLocateConflict two lanes disagreed or one found no column.
+constexpr uint32_t kLocateConflict = 0xFFFFFFFFu;
+struct LocateArgs {
+    VerifyArgs v;                 // data, recovery, G, shape and lanes (span, nch) as the scrub's
+    uint32_t *votes;              // workspace, stripes words
+    int8_t *status;               // stripes: 0 clean, 1 rows[s] is the corrupt block, 2 no single block
+    uint8_t *rows;                // stripes: the row (data x, recovery k + r), else 0xFF
+};
+
 // Repair (cauchy_256_reconstruct_batch): out_j = sum_slot B(C[j][slot]) block_slot over the k
 // survivor slots of a stripe, for its `want` wanted rows.  lh_reconstruct_coef_kernel validates
 // the stripe (survivor rows distinct and < k + m, wanted rows < k + m or 0xFF), writes status[s],
@@ -281,6 +296,7 @@ hipError_t launch_plan(const PlanArgs &a, hipStream_t st);
 hipError_t launch_ptr_copy(const PtrCopyArgs &a, hipStream_t st);
 hipError_t launch_update(const UpdateArgs &a, hipStream_t st);
 hipError_t launch_verify(const VerifyArgs &a, hipStream_t st);
+hipError_t launch_locate(const LocateArgs &a, hipStream_t st);
 hipError_t launch_reconstruct(const ReconstructArgs &a, hipStream_t st);
 
 }  // namespace lh
