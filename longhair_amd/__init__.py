@@ -259,6 +259,29 @@ def update_batch_ptrs(k, m, block_bytes, cols, old_ptrs, new_ptrs, recovery_ptrs
     return status
 
 
+def _stored_stripes(data, recovery):
+    """The stored stripes of verify_batch and locate_batch, checked: (stripes, k, m, block_bytes)."""
+    _block_tensor(data, "data")
+    _block_tensor(recovery, "recovery")
+    stripes, k, nbytes = data.shape
+    m = recovery.shape[1]
+    _require(tuple(recovery.shape) == (stripes, m, nbytes), f"recovery must be [{stripes}, m, {nbytes}]")
+    _require(recovery.device == data.device, "recovery must be on data's device")
+    return stripes, k, m, nbytes
+
+
+def _stored_tables(k, m, data_ptrs, recovery_ptrs):
+    """The same of the pointer-table forms: (stripes, data table, recovery table) for the C call."""
+    import torch
+    _cuda_tensor(data_ptrs, torch.int64, "data_ptrs")
+    _require(data_ptrs.dim() == 2, "data_ptrs must be [stripes, k]")
+    stripes = data_ptrs.shape[0]
+    data_t = _ptr_table(data_ptrs, stripes, k, "data_ptrs")
+    rec_t = _ptr_table(recovery_ptrs, stripes, m, "recovery_ptrs")
+    _require(recovery_ptrs.device == data_ptrs.device, "recovery_ptrs must be on data_ptrs' device")
+    return stripes, data_t, rec_t
+
+
 def _verify_outputs(stripes, m, status, bad_rows, device):
     import torch
     if status is None:
@@ -278,12 +301,7 @@ def verify_batch(data, recovery, status=None, bad_rows=None, stream=None):
     bad_rows: optional uint8 CUDA tensor [stripes, m], contiguous: 1 where recovery row r differs
               from what encode_batch writes for the stored data, else 0.
     Returns `status` (int8 [stripes], allocated if not given): 0 every row intact, 1 some row bad."""
-    _block_tensor(data, "data")
-    _block_tensor(recovery, "recovery")
-    stripes, k, nbytes = data.shape
-    m = recovery.shape[1]
-    _require(tuple(recovery.shape) == (stripes, m, nbytes), f"recovery must be [{stripes}, m, {nbytes}]")
-    _require(recovery.device == data.device, "recovery must be on data's device")
+    stripes, k, m, nbytes = _stored_stripes(data, recovery)
     status, rows_p = _verify_outputs(stripes, m, status, bad_rows, data.device)
     rc = lib().cauchy_256_verify_batch(k, m, nbytes, stripes, ctypes.c_void_p(data.data_ptr()),
                                        ctypes.c_longlong(data.stride(0)), ctypes.c_void_p(recovery.data_ptr()),
@@ -300,13 +318,7 @@ def verify_batch_ptrs(k, m, block_bytes, data_ptrs, recovery_ptrs, status=None, 
     data_ptrs:     int64 CUDA tensor [stripes, k] of device addresses;
     recovery_ptrs: int64 CUDA tensor [stripes, m].
     Returns `status` (int8 [stripes]); `bad_rows` (uint8 [stripes, m]) is filled when given."""
-    import torch
-    _cuda_tensor(data_ptrs, torch.int64, "data_ptrs")
-    _require(data_ptrs.dim() == 2, "data_ptrs must be [stripes, k]")
-    stripes = data_ptrs.shape[0]
-    data_t = _ptr_table(data_ptrs, stripes, k, "data_ptrs")
-    rec_t = _ptr_table(recovery_ptrs, stripes, m, "recovery_ptrs")
-    _require(recovery_ptrs.device == data_ptrs.device, "recovery_ptrs must be on data_ptrs' device")
+    stripes, data_t, rec_t = _stored_tables(k, m, data_ptrs, recovery_ptrs)
     status, rows_p = _verify_outputs(stripes, m, status, bad_rows, data_ptrs.device)
     rc = lib().cauchy_256_verify_batch_ptrs(k, m, block_bytes, stripes, data_t, rec_t, ctypes.c_void_p(status.data_ptr()),
                                             rows_p, ctypes.c_void_p(_stream_handle(stream)))
@@ -343,12 +355,7 @@ def locate_batch(data, recovery, status=None, rows=None, stream=None):
         reconstruct_batch(survivors, survivor_rows, m, rows.unsqueeze(1), out)
 
     with, per stripe, any k blocks other than the located one as survivors."""
-    _block_tensor(data, "data")
-    _block_tensor(recovery, "recovery")
-    stripes, k, nbytes = data.shape
-    m = recovery.shape[1]
-    _require(tuple(recovery.shape) == (stripes, m, nbytes), f"recovery must be [{stripes}, m, {nbytes}]")
-    _require(recovery.device == data.device, "recovery must be on data's device")
+    stripes, k, m, nbytes = _stored_stripes(data, recovery)
     status, rows = _locate_outputs(stripes, status, rows, data.device)
     rc = lib().cauchy_256_locate_batch(k, m, nbytes, stripes, ctypes.c_void_p(data.data_ptr()),
                                        ctypes.c_longlong(data.stride(0)), ctypes.c_void_p(recovery.data_ptr()),
@@ -365,13 +372,7 @@ def locate_batch_ptrs(k, m, block_bytes, data_ptrs, recovery_ptrs, status=None, 
     data_ptrs:     int64 CUDA tensor [stripes, k] of device addresses;
     recovery_ptrs: int64 CUDA tensor [stripes, m].
     Returns (status, rows) as locate_batch."""
-    import torch
-    _cuda_tensor(data_ptrs, torch.int64, "data_ptrs")
-    _require(data_ptrs.dim() == 2, "data_ptrs must be [stripes, k]")
-    stripes = data_ptrs.shape[0]
-    data_t = _ptr_table(data_ptrs, stripes, k, "data_ptrs")
-    rec_t = _ptr_table(recovery_ptrs, stripes, m, "recovery_ptrs")
-    _require(recovery_ptrs.device == data_ptrs.device, "recovery_ptrs must be on data_ptrs' device")
+    stripes, data_t, rec_t = _stored_tables(k, m, data_ptrs, recovery_ptrs)
     status, rows = _locate_outputs(stripes, status, rows, data_ptrs.device)
     rc = lib().cauchy_256_locate_batch_ptrs(k, m, block_bytes, stripes, data_t, rec_t, ctypes.c_void_p(status.data_ptr()),
                                             ctypes.c_void_p(rows.data_ptr()), ctypes.c_void_p(_stream_handle(stream)))

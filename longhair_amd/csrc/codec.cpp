@@ -355,7 +355,48 @@ struct Blocks {
     uint8_t *const *ptrs() const { return (uint8_t *const *)p; }
 };
 static Blocks strided_blocks(const void *p, long long stride) { return {p, stride, false}; }
-static Blocks table_blocks(uint8_t *const *ptrs, int n) { return {ptrs, (long long)n * 8, true}; }
+static Blocks table_blocks(const void *ptrs, int n) { return {ptrs, (long long)n * 8, true}; }
+
+// One array of a maintenance call (update, verify, locate, reconstruct), n blocks per stripe: the
+// strided form's stride is checked for every stripe count, a null array only refused where there
+// are stripes to read.
+static int check_blocks(const Blocks &b, long long n, int bytes, int stripes, const char *name) {
+    if (!b.table && b.stride < n * bytes) return fail(kInvalid, std::string(name) + " stride smaller than the stripe");
+    if (stripes > 0 && !b.p) return fail(kInvalid, std::string("null ") + name + " argument");
+    return kOk;
+}
+
+// The array into its fields of a maintenance call's argument block (the other form's stay 0).
+template <class P, class T>
+static void put_blocks(const Blocks &b, P &p, long long &stride, T &ptrs) {
+    if (b.table) {
+        ptrs = (T)b.p;
+    } else {
+        p = (P)b.p;
+        stride = b.stride;
+    }
+}
+
+// The shape rules the maintenance calls share; *flat: every coefficient is 0 or 1 (m == 1 or
+// k == 1), the plain XOR of blocks of any size, no generator.  Otherwise B(c) runs over the
+// block's 8 sub-blocks.
+static int check_coded_shape(int k, int m, int bytes, int stripes, int *flat) {
+    if (int rc = check_shape(k, m, bytes, stripes)) return rc;
+    *flat = (m == 1 || k == 1) ? 1 : 0;
+    if (!*flat && (k + m > 256 || bytes % 8 != 0)) return fail(kInvalid, "k + m > 256 or block_bytes % 8 != 0");
+    return kOk;
+}
+
+// A zero page of at least n bytes for the clearing copies of launch_verify and launch_locate,
+// grown by doubling from 64 so that batches of growing size leave few retired pages (zero_page
+// never frees one).  Under capture the page must be large enough already: the call fails with
+// the stream untouched (an uncaptured call of the same size first, or
+// cauchy_256_batch_prepare_stream).
+static int clearing_zero_page(Device *d, size_t n, const uint8_t **out, hipStream_t st) {
+    size_t need = 64;
+    while (need < n) need *= 2;
+    return zero_page(d, need, out, st);
+}
 
 // The in / out side of the generic launchers' argument blocks (the other form's fields stay 0).
 static void set_in(JumpApplyArgs &a, const Blocks &b) {
@@ -953,23 +994,26 @@ static int decode_batch_ptrs(int k, int m, int bytes, int stripes, uint8_t *cons
 // ------------------------------------------------------------------ recovery patch
 // cauchy_256_update_batch / _ptrs (include/cauchy_256_update.h): one launch of lh_update_kernel.
 // Every check comes before the device, so it holds without one.
-static int update_batch(int k, int m, int bytes, int stripes, int changes, const uint8_t *d_cols, UpdateArgs a,
-                        hipStream_t st) {
-    if (k < 1 || k > 255 || m < 1) return fail(kInvalid, "invalid k (1..255: a column is one byte, 0xFF reserved) or m");
-    if (bytes <= 0 || stripes < 0 || changes < 0 || changes > 255)
-        return fail(kInvalid, "invalid block_bytes, stripes or changes (0..255)");
-    const bool table = a.table != 0;
-    if (stripes > 0 && changes > 0 &&
-        (!d_cols || !(table ? (const void *)a.old_ptrs : (const void *)a.old_blocks) ||
-         !(table ? (const void *)a.rec_ptrs : (const void *)a.rec)))
-        return fail(kInvalid, "null cols, old or recovery argument");
-    if (!table) {
-        if (a.old_stride < (long long)changes * bytes || (a.new_blocks && a.new_stride < (long long)changes * bytes))
-            return fail(kInvalid, "old or new stride smaller than the stripe's changed blocks");
-        if (a.rec_stride < (long long)m * bytes) return fail(kInvalid, "recovery stride smaller than the stripe");
-    }
-    if (m > 1 && (k + m > 256 || bytes % 8 != 0)) return fail(kInvalid, "k + m > 256 or block_bytes % 8 != 0");
-    if (stripes == 0 || changes == 0) return kOk;
+static int update_batch(int k, int m, int bytes, int stripes, int changes, const uint8_t *d_cols, const Blocks &old,
+                        const Blocks &neu, const Blocks &rec, int8_t *d_status, hipStream_t st) {
+    UpdateArgs a{};
+    if (int rc = check_coded_shape(k, m, bytes, stripes, &a.flat)) return rc;
+    if (k > 255) return fail(kInvalid, "invalid k (1..255: a column is one byte, 0xFF reserved)");
+    if (changes < 0 || changes > 255) return fail(kInvalid, "invalid changes (0..255)");
+    if (k == 1 && m > 1 && (m > 255 || bytes % 8 != 0))  // (the patch alone refuses what its flat kernel would take)
+        return fail(kInvalid, "k + m > 256 or block_bytes % 8 != 0");
+    const int work = changes > 0 ? stripes : 0;
+    if (work > 0 && !d_cols) return fail(kInvalid, "null cols argument");
+    if (int rc = check_blocks(old, changes, bytes, work, "old")) return rc;
+    if (neu.p)  // (null: old holds the deltas)
+        if (int rc = check_blocks(neu, changes, bytes, work, "new")) return rc;
+    if (int rc = check_blocks(rec, m, bytes, work, "recovery")) return rc;
+    if (work == 0) return kOk;
+    a.table = old.table;
+    put_blocks(old, a.old_blocks, a.old_stride, a.old_ptrs);
+    put_blocks(neu, a.new_blocks, a.new_stride, a.new_ptrs);
+    put_blocks(rec, a.rec, a.rec_stride, a.rec_ptrs);
+    a.status = d_status;
     Device *d = nullptr;
     if (int rc = current_device(&d)) return rc;
     a.cols = d_cols;
@@ -978,7 +1022,6 @@ static int update_batch(int k, int m, int bytes, int stripes, int changes, const
     a.changes = changes;
     a.bytes = bytes;
     a.stripes = stripes;
-    a.flat = (m == 1 || k == 1) ? 1 : 0;  // every coefficient is 1: the plain XOR of the deltas
     if (!a.flat)
         if (int rc = device_generator(d, k, m, &a.G, nullptr, st)) return rc;
     LH_HIP(launch_update(a, st));  // (a batch of more than 2^31 - 1 workgroups: hipErrorInvalidValue)
@@ -988,34 +1031,35 @@ static int update_batch(int k, int m, int bytes, int stripes, int changes, const
 // ------------------------------------------------------------------ recovery scrub
 // cauchy_256_verify_batch / _ptrs (include/cauchy_256_verify.h): two clearing copies and one launch of
 // lh_verify_kernel.  Every check comes before the device, so it holds without one.
-static int verify_batch(int k, int m, int bytes, int stripes, VerifyArgs a, hipStream_t st) {
-    if (k < 1 || k > 256 || m < 1 || m > 256) return fail(kInvalid, "invalid k or m (1..256)");
-    if (bytes <= 0 || stripes < 0) return fail(kInvalid, "invalid block_bytes or stripes");
-    if (m > 1 && k > 1 && (k + m > 256 || bytes % 8 != 0)) return fail(kInvalid, "k + m > 256 or block_bytes % 8 != 0");
-    const bool table = a.table != 0;
-    if (!table) {
-        if (a.data_stride < (long long)k * bytes) return fail(kInvalid, "data stride smaller than the stripe");
-        if (a.rec_stride < (long long)m * bytes) return fail(kInvalid, "recovery stride smaller than the stripe");
-    }
+// What cauchy_256_verify_batch and cauchy_256_locate_batch check alike: the shape and the two arrays.
+// Fills v's shape, `flat` and arrays.
+static int check_stored(int k, int m, int bytes, int stripes, const Blocks &data, const Blocks &rec, VerifyArgs &v) {
+    if (int rc = check_coded_shape(k, m, bytes, stripes, &v.grid.flat)) return rc;
+    if (int rc = check_blocks(data, k, bytes, stripes, "data")) return rc;
+    if (int rc = check_blocks(rec, m, bytes, stripes, "recovery")) return rc;
+    v.table = data.table;
+    put_blocks(data, v.data, v.data_stride, v.data_ptrs);
+    put_blocks(rec, v.rec, v.rec_stride, v.rec_ptrs);
+    v.k = k;
+    v.m = m;
+    v.bytes = bytes;
+    v.stripes = stripes;
+    return kOk;
+}
+
+static int verify_batch(int k, int m, int bytes, int stripes, const Blocks &data, const Blocks &rec, int8_t *d_status,
+                        uint8_t *d_bad_rows, hipStream_t st) {
+    VerifyArgs a{};
+    a.status = d_status;
+    a.bad_rows = d_bad_rows;
+    if (int rc = check_stored(k, m, bytes, stripes, data, rec, a)) return rc;
     if (!a.status && !a.bad_rows) return fail(kInvalid, "null status and bad_rows: no output");
-    if (stripes > 0 && (!(table ? (const void *)a.data_ptrs : (const void *)a.data) ||
-                        !(table ? (const void *)a.rec_ptrs : (const void *)a.rec)))
-        return fail(kInvalid, "null data or recovery argument");
     if (stripes == 0) return kOk;
     Device *d = nullptr;
     if (int rc = current_device(&d)) return rc;
-    a.k = k;
-    a.m = m;
-    a.bytes = bytes;
-    a.stripes = stripes;
-    a.flat = (m == 1 || k == 1) ? 1 : 0;  // every coefficient is 1: recovery_r against the XOR of the data
-    if (!a.flat)
+    if (!a.grid.flat)
         if (int rc = device_generator(d, k, m, &a.G, nullptr, st)) return rc;
-    // launch_verify zeroes both outputs by copies from the zero page (grown by doubling: few
-    // retired pages; under capture it must be large enough already)
-    size_t need = 64;
-    while (need < (size_t)stripes * (a.bad_rows ? m : 1)) need *= 2;
-    if (int rc = zero_page(d, need, &a.zero, st)) return rc;
+    if (int rc = clearing_zero_page(d, (size_t)stripes * (a.bad_rows ? m : 1), &a.zero, st)) return rc;
     LH_HIP(launch_verify(a, st));  // (a batch of more than 2^31 - 1 workgroups: hipErrorInvalidValue)
     return kOk;
 }
@@ -1027,37 +1071,24 @@ static int verify_batch(int k, int m, int bytes, int stripes, VerifyArgs a, hipS
 // stripes vote words; the zero page clears both.  Generator, zero page and workspace are all
 // settled before anything is enqueued, so a captured call that would have to allocate returns
 // with the stream untouched.
-static int locate_batch(int k, int m, int bytes, int stripes, LocateArgs a, hipStream_t st) {
-    if (k < 1 || k > 256 || m < 1 || m > 256) return fail(kInvalid, "invalid k or m (1..256)");
-    if (bytes <= 0 || stripes < 0) return fail(kInvalid, "invalid block_bytes or stripes");
-    if (m > 1 && k > 1 && bytes % 8 != 0) return fail(kInvalid, "block_bytes % 8 != 0");
-    if (m >= 2 && k + m > 255) return fail(kInvalid, "k + m > 255 (a row is one byte, 0xFF reserved)");
+static int locate_batch(int k, int m, int bytes, int stripes, const Blocks &data, const Blocks &rec, int8_t *d_status,
+                        uint8_t *d_rows, hipStream_t st) {
+    LocateArgs a{};
+    a.status = d_status;
+    a.rows = d_rows;
     VerifyArgs &v = a.v;
-    const bool table = v.table != 0;
-    if (!table) {
-        if (v.data_stride < (long long)k * bytes) return fail(kInvalid, "data stride smaller than the stripe");
-        if (v.rec_stride < (long long)m * bytes) return fail(kInvalid, "recovery stride smaller than the stripe");
-    }
+    if (int rc = check_stored(k, m, bytes, stripes, data, rec, v)) return rc;
+    if (m >= 2 && k + m > 255) return fail(kInvalid, "k + m > 255 (a row is one byte, 0xFF reserved)");
     if (!a.status || !a.rows) return fail(kInvalid, "null status or rows: both outputs are required");
-    if (stripes > 0 && (!(table ? (const void *)v.data_ptrs : (const void *)v.data) ||
-                        !(table ? (const void *)v.rec_ptrs : (const void *)v.rec)))
-        return fail(kInvalid, "null data or recovery argument");
     if (stripes == 0) return kOk;
     Device *d = nullptr;
     if (int rc = current_device(&d)) return rc;
-    v.k = k;
-    v.m = m;
-    v.bytes = bytes;
-    v.stripes = stripes;
-    v.flat = (m == 1 || k == 1) ? 1 : 0;  // every coefficient is 1
     const size_t bad_bytes = ((size_t)stripes * m + 15) & ~(size_t)15, vote_bytes = (size_t)stripes * sizeof(uint32_t);
     Workspace *w = nullptr;
     if (int rc = workspace(d, st, 0, bad_bytes + vote_bytes, &w)) return rc;
-    if (!v.flat)
+    if (!v.grid.flat)
         if (int rc = device_generator(d, k, m, &v.G, nullptr, st)) return rc;
-    size_t need = 64;
-    while (need < std::max((size_t)stripes * m, vote_bytes)) need *= 2;
-    if (int rc = zero_page(d, need, &v.zero, st)) return rc;
+    if (int rc = clearing_zero_page(d, std::max((size_t)stripes * m, vote_bytes), &v.zero, st)) return rc;
     v.status = nullptr;
     v.bad_rows = w->work.ptr;
     a.votes = (uint32_t *)(w->work.ptr + bad_bytes);
@@ -1072,23 +1103,23 @@ static int locate_batch(int k, int m, int bytes, int stripes, LocateArgs a, hipS
 // stream's workspace holds the plans and, in `work`, the rows' copy, valid[stripes] and the
 // stripes * want * k coefficient bytes, so a captured call never allocates (workspace()).
 static int reconstruct_batch(int k, int m, int bytes, int stripes, int want, const uint8_t *d_rows,
-                             const uint8_t *d_want_rows, ReconstructArgs a, hipStream_t st) {
-    if (k < 1 || k > 256 || m < 1 || m > 256) return fail(kInvalid, "invalid k or m (1..256)");
-    if (bytes <= 0 || stripes < 0 || want < 1) return fail(kInvalid, "invalid block_bytes, stripes or want");
+                             const uint8_t *d_want_rows, const Blocks &blocks, const Blocks &out, int8_t *d_status,
+                             hipStream_t st) {
+    ReconstructArgs a{};
+    if (int rc = check_coded_shape(k, m, bytes, stripes, &a.grid.flat)) return rc;
+    if (want < 1) return fail(kInvalid, "invalid want");
     if (k + m > 255) return fail(kInvalid, "k + m > 255 (a row is one byte, 0xFF reserved)");
     if ((long long)want * k > 0x7FFFFFFF) return fail(kInvalid, "want * k > 2^31 - 1 (a stripe's coefficients are indexed by an int)");
-    if (m > 1 && k > 1 && bytes % 8 != 0) return fail(kInvalid, "block_bytes % 8 != 0");
-    const bool table = a.table != 0;
-    if (!table) {
-        if (a.blocks_stride < (long long)k * bytes) return fail(kInvalid, "blocks stride smaller than the stripe");
-        if (a.out_stride < (long long)want * bytes) return fail(kInvalid, "out stride smaller than the wanted blocks");
-    }
-    if (stripes > 0 && (!(table ? (const void *)a.block_ptrs : (const void *)a.blocks) || !d_rows || !d_want_rows ||
-                        !(table ? (const void *)a.out_ptrs : (const void *)a.out)))
-        return fail(kInvalid, "null blocks, rows, want_rows or out argument");
+    if (int rc = check_blocks(blocks, k, bytes, stripes, "blocks")) return rc;
+    if (int rc = check_blocks(out, want, bytes, stripes, "out")) return rc;
+    if (stripes > 0 && (!d_rows || !d_want_rows)) return fail(kInvalid, "null rows or want_rows argument");
     if (stripes == 0) return kOk;
     Device *d = nullptr;
     if (int rc = current_device(&d)) return rc;
+    a.table = blocks.table;
+    put_blocks(blocks, a.blocks, a.blocks_stride, a.block_ptrs);
+    put_blocks(out, a.out, a.out_stride, a.out_ptrs);
+    a.status = d_status;
     a.rows = d_rows;
     a.want_rows = d_want_rows;
     a.k = k;
@@ -1096,16 +1127,15 @@ static int reconstruct_batch(int k, int m, int bytes, int stripes, int want, con
     a.want = want;
     a.bytes = bytes;
     a.stripes = stripes;
-    a.flat = (m == 1 || k == 1) ? 1 : 0;  // every coefficient is 0 or 1: no plan
     a.gf_exp = d->gf_exp;
     a.gf_log = d->gf_log;
     const int e_max = k < m ? k : m;
     const size_t rows_bytes = ((size_t)stripes * k + 15) & ~(size_t)15, valid_bytes = ((size_t)stripes + 15) & ~(size_t)15;
     const size_t work_bytes = rows_bytes + valid_bytes + (size_t)stripes * want * k;
-    const size_t plan_bytes = a.flat ? 16 : plan_workspace_bytes(k, m, e_max, stripes);
+    const size_t plan_bytes = a.grid.flat ? 16 : plan_workspace_bytes(k, m, e_max, stripes);
     Workspace *w = nullptr;
     if (int rc = workspace(d, st, plan_bytes, work_bytes, &w)) return rc;
-    if (!a.flat) {
+    if (!a.grid.flat) {
         if (int rc = device_generator(d, k, m, &a.G, nullptr, st)) return rc;
         LH_HIP(hipMemcpyAsync(w->work.ptr, d_rows, (size_t)stripes * k, hipMemcpyDeviceToDevice, st));
         if (int rc = run_planner(d, st, k, m, e_max, stripes, w->work.ptr, nullptr, work_bytes, true, &w)) return rc;
@@ -1676,15 +1706,9 @@ LH_API int cauchy_256_update_batch(int k, int m, int block_bytes, int stripes, i
                                    void *d_recovery, long long recovery_stride, signed char *d_status, void *stream) {
     LH_TRY
         lh::LaunchTrace trace;
-        lh::UpdateArgs a{};
-        a.old_blocks = (const uint8_t *)d_old;
-        a.old_stride = old_stride;
-        a.new_blocks = (const uint8_t *)d_new;
-        a.new_stride = new_stride;
-        a.rec = (uint8_t *)d_recovery;
-        a.rec_stride = recovery_stride;
-        a.status = (int8_t *)d_status;
-        return lh::update_batch(k, m, block_bytes, stripes, changes, d_cols, a, (hipStream_t)stream);
+        return lh::update_batch(k, m, block_bytes, stripes, changes, d_cols, lh::strided_blocks(d_old, old_stride),
+                                lh::strided_blocks(d_new, new_stride), lh::strided_blocks(d_recovery, recovery_stride),
+                                (int8_t *)d_status, (hipStream_t)stream);
     LH_CATCH
 }
 
@@ -1694,13 +1718,9 @@ LH_API int cauchy_256_update_batch_ptrs(int k, int m, int block_bytes, int strip
                                         signed char *d_status, void *stream) {
     LH_TRY
         lh::LaunchTrace trace;
-        lh::UpdateArgs a{};
-        a.old_ptrs = (const uint8_t *const *)d_old_ptrs;
-        a.new_ptrs = (const uint8_t *const *)d_new_ptrs;
-        a.rec_ptrs = (uint8_t *const *)d_recovery_ptrs;
-        a.status = (int8_t *)d_status;
-        a.table = 1;
-        return lh::update_batch(k, m, block_bytes, stripes, changes, d_cols, a, (hipStream_t)stream);
+        return lh::update_batch(k, m, block_bytes, stripes, changes, d_cols, lh::table_blocks(d_old_ptrs, changes),
+                                lh::table_blocks(d_new_ptrs, changes), lh::table_blocks(d_recovery_ptrs, m),
+                                (int8_t *)d_status, (hipStream_t)stream);
     LH_CATCH
 }
 
@@ -1709,14 +1729,9 @@ LH_API int cauchy_256_verify_batch(int k, int m, int block_bytes, int stripes, c
                                    unsigned char *d_bad_rows, void *stream) {
     LH_TRY
         lh::LaunchTrace trace;
-        lh::VerifyArgs a{};
-        a.data = (const uint8_t *)d_data;
-        a.data_stride = data_stride;
-        a.rec = (const uint8_t *)d_recovery;
-        a.rec_stride = recovery_stride;
-        a.status = (int8_t *)d_status;
-        a.bad_rows = d_bad_rows;
-        return lh::verify_batch(k, m, block_bytes, stripes, a, (hipStream_t)stream);
+        return lh::verify_batch(k, m, block_bytes, stripes, lh::strided_blocks(d_data, data_stride),
+                                lh::strided_blocks(d_recovery, recovery_stride), (int8_t *)d_status, d_bad_rows,
+                                (hipStream_t)stream);
     LH_CATCH
 }
 
@@ -1725,13 +1740,8 @@ LH_API int cauchy_256_verify_batch_ptrs(int k, int m, int block_bytes, int strip
                                         unsigned char *d_bad_rows, void *stream) {
     LH_TRY
         lh::LaunchTrace trace;
-        lh::VerifyArgs a{};
-        a.data_ptrs = (const uint8_t *const *)d_data_ptrs;
-        a.rec_ptrs = (const uint8_t *const *)d_recovery_ptrs;
-        a.status = (int8_t *)d_status;
-        a.bad_rows = d_bad_rows;
-        a.table = 1;
-        return lh::verify_batch(k, m, block_bytes, stripes, a, (hipStream_t)stream);
+        return lh::verify_batch(k, m, block_bytes, stripes, lh::table_blocks(d_data_ptrs, k),
+                                lh::table_blocks(d_recovery_ptrs, m), (int8_t *)d_status, d_bad_rows, (hipStream_t)stream);
     LH_CATCH
 }
 
@@ -1740,14 +1750,9 @@ LH_API int cauchy_256_locate_batch(int k, int m, int block_bytes, int stripes, c
                                    unsigned char *d_rows, void *stream) {
     LH_TRY
         lh::LaunchTrace trace;
-        lh::LocateArgs a{};
-        a.v.data = (const uint8_t *)d_data;
-        a.v.data_stride = data_stride;
-        a.v.rec = (const uint8_t *)d_recovery;
-        a.v.rec_stride = recovery_stride;
-        a.status = (int8_t *)d_status;
-        a.rows = d_rows;
-        return lh::locate_batch(k, m, block_bytes, stripes, a, (hipStream_t)stream);
+        return lh::locate_batch(k, m, block_bytes, stripes, lh::strided_blocks(d_data, data_stride),
+                                lh::strided_blocks(d_recovery, recovery_stride), (int8_t *)d_status, d_rows,
+                                (hipStream_t)stream);
     LH_CATCH
 }
 
@@ -1756,13 +1761,8 @@ LH_API int cauchy_256_locate_batch_ptrs(int k, int m, int block_bytes, int strip
                                         unsigned char *d_rows, void *stream) {
     LH_TRY
         lh::LaunchTrace trace;
-        lh::LocateArgs a{};
-        a.v.data_ptrs = (const uint8_t *const *)d_data_ptrs;
-        a.v.rec_ptrs = (const uint8_t *const *)d_recovery_ptrs;
-        a.v.table = 1;
-        a.status = (int8_t *)d_status;
-        a.rows = d_rows;
-        return lh::locate_batch(k, m, block_bytes, stripes, a, (hipStream_t)stream);
+        return lh::locate_batch(k, m, block_bytes, stripes, lh::table_blocks(d_data_ptrs, k),
+                                lh::table_blocks(d_recovery_ptrs, m), (int8_t *)d_status, d_rows, (hipStream_t)stream);
     LH_CATCH
 }
 
@@ -1772,13 +1772,9 @@ LH_API int cauchy_256_reconstruct_batch(int k, int m, int block_bytes, int strip
                                         signed char *d_status, void *stream) {
     LH_TRY
         lh::LaunchTrace trace;
-        lh::ReconstructArgs a{};
-        a.blocks = (const uint8_t *)d_blocks;
-        a.blocks_stride = blocks_stride;
-        a.out = (uint8_t *)d_out;
-        a.out_stride = out_stride;
-        a.status = (int8_t *)d_status;
-        return lh::reconstruct_batch(k, m, block_bytes, stripes, want, d_rows, d_want_rows, a, (hipStream_t)stream);
+        return lh::reconstruct_batch(k, m, block_bytes, stripes, want, d_rows, d_want_rows,
+                                     lh::strided_blocks(d_blocks, blocks_stride), lh::strided_blocks(d_out, out_stride),
+                                     (int8_t *)d_status, (hipStream_t)stream);
     LH_CATCH
 }
 
@@ -1787,12 +1783,8 @@ LH_API int cauchy_256_reconstruct_batch_ptrs(int k, int m, int block_bytes, int 
                                              void *const *d_out_ptrs, signed char *d_status, void *stream) {
     LH_TRY
         lh::LaunchTrace trace;
-        lh::ReconstructArgs a{};
-        a.block_ptrs = (const uint8_t *const *)d_block_ptrs;
-        a.out_ptrs = (uint8_t *const *)d_out_ptrs;
-        a.status = (int8_t *)d_status;
-        a.table = 1;
-        return lh::reconstruct_batch(k, m, block_bytes, stripes, want, d_rows, d_want_rows, a, (hipStream_t)stream);
+        return lh::reconstruct_batch(k, m, block_bytes, stripes, want, d_rows, d_want_rows, lh::table_blocks(d_block_ptrs, k),
+                                     lh::table_blocks(d_out_ptrs, want), (int8_t *)d_status, (hipStream_t)stream);
     LH_CATCH
 }
 

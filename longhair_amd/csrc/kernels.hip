@@ -245,6 +245,25 @@ namespace {
 
 constexpr int kUpdateLane = 8;  // bytes per lane and sub-block
 
+// Where lane c's W-byte window starts in each sub-block: c W, the last lane's window ends with the span.
+template <int W>
+__device__ __forceinline__ int lh_lane_at(int span, int c) {
+    return min(c * W, max(span - W, 0));
+}
+
+// The workgroup's 256-lane chunk and its row tile: workgroups b, b + 8, b + 16, ... of the grid are
+// the tiles of chunk (b / (8 tiles)) * 8 + b % 8 (why: lh_verify_kernel; lane_grid pads the grid so).
+__device__ __forceinline__ long long lh_chunk_of(const lh::LaneGrid &g, int &tile) {
+    long long chunk = blockIdx.x;
+    tile = 0;
+    if (g.tiles > 1) {
+        const long long q = chunk >> 3;
+        tile = (int)(q % g.tiles);
+        chunk = (q / g.tiles) * 8 + (chunk & 7);
+    }
+    return chunk;
+}
+
 // The first rem < W bytes at p (the rest zero) in 8-, 4-, 2- and 1-byte accesses.
 template <int W>
 __device__ __forceinline__ Word<W> wload_tail(const uint8_t *p, int rem) {
@@ -401,7 +420,7 @@ __device__ __forceinline__ void lh_mul_acc(Word<W> (&acc)[8], const Word<W> (&v)
 template <int W, int NS, bool PTR>
 __device__ __forceinline__ void lh_update_lane(const lh::UpdateArgs &a, long long s, int c) {
     constexpr int TO = lh::kGenericTileOut;
-    const int at = min(c * W, max(a.span - W, 0));  // (the last lane's window ends with the span)
+    const int at = lh_lane_at<W>(a.span, c);
     const long long e0 = s * a.changes;
     const bool two = PTR ? a.new_ptrs != nullptr : a.new_blocks != nullptr;
     for (int i0 = 0; i0 < a.m; i0 += TO) {
@@ -477,10 +496,9 @@ __global__ void __launch_bounds__(256) lh_update_kernel(lh::UpdateArgs a) {
 // recovery words to "is any bit set": k + m blocks read, one byte stored per bad row and stripe
 // into outputs the launcher zeroed on the same stream (every writer of a byte writes 1, so no
 // atomics), no scratch.
-//  * Lanes as in lh_update_kernel: flat over (stripe, 8-byte column of each sub-block).  Nothing
-//    is stored back, so the stripe's last lane, when span % 8 != 0, just takes the 8 bytes that
-//    end the span (comparing its neighbour's bytes again harms nothing); a span under 8 bytes is
-//    loaded piecewise, data and recovery zero-padded alike.
+//  * The lanes of lh_update_kernel (defined there; lh::LaneGrid, lh_lane_at).  Nothing is stored
+//    back, so the last lane's window needs no care (comparing its neighbour's bytes again harms
+//    nothing); a span under a lane is loaded piecewise, data and recovery zero-padded alike.
 //  * The column is the loop index and G is the same for every stripe, so G[r][j] is wave-uniform:
 //    a scalar (readfirstlane), and a zero coefficient bit a uniform branch around its 16 XORs
 //    (half the bits of a Cauchy coefficient on average: 8.2 against 16.0 ms with the masked
@@ -515,22 +533,22 @@ __device__ __forceinline__ const uint8_t *lh_verify_rec(const lh::VerifyArgs &a,
 template <int W, bool PTR>
 __device__ __forceinline__ void lh_verify_lane(const lh::VerifyArgs &a, long long s, int c, int i0, int ni) {
     constexpr int TO = lh::kGenericTileOut;
-    const int at = min(c * W, max(a.span - W, 0));  // (the last lane's window ends with the span)
+    const int at = lh_lane_at<W>(a.grid.span, c);
     Word<W> acc[TO][8];
 #pragma unroll
     for (int i = 0; i < TO; ++i)
-        if (i < ni) lh_update_load<W, 8>(acc[i], lh_verify_rec<PTR>(a, s, i0 + i), at, a.span);
+        if (i < ni) lh_update_load<W, 8>(acc[i], lh_verify_rec<PTR>(a, s, i0 + i), at, a.grid.span);
     const uint8_t *g = a.G + (long long)i0 * a.k;
     Word<W> cur[8];
     uint32_t e[TO];
-    lh_update_load<W, 8>(cur, lh_verify_data<PTR>(a, s, 0), at, a.span);
+    lh_update_load<W, 8>(cur, lh_verify_data<PTR>(a, s, 0), at, a.grid.span);
 #pragma unroll
     for (int i = 0; i < TO; ++i) e[i] = i < ni ? g[i * a.k] : 0;
     for (int j = 0; j < a.k; ++j) {
         const int jn = j + 1 < a.k ? j + 1 : j;  // (the last column reloads itself)
         Word<W> nxt[8];
         uint32_t en[TO];
-        lh_update_load<W, 8>(nxt, lh_verify_data<PTR>(a, s, jn), at, a.span);
+        lh_update_load<W, 8>(nxt, lh_verify_data<PTR>(a, s, jn), at, a.grid.span);
 #pragma unroll
         for (int i = 0; i < TO; ++i) en[i] = i < ni ? g[i * a.k + jn] : 0;
         Word<W> v[15];
@@ -562,15 +580,15 @@ __device__ __forceinline__ void lh_verify_lane(const lh::VerifyArgs &a, long lon
 template <bool PTR>
 __device__ __forceinline__ void lh_verify_flat(const lh::VerifyArgs &a, long long s, int c) {
     constexpr int W = 16;
-    const int at = min(c * W, max(a.span - W, 0));
+    const int at = lh_lane_at<W>(a.grid.span, c);
     Word<W> x[1], d[1];
     wzero(x[0]);
     for (int j = 0; j < a.k; ++j) {
-        lh_update_load<W, 1>(d, lh_verify_data<PTR>(a, s, j), at, a.span);
+        lh_update_load<W, 1>(d, lh_verify_data<PTR>(a, s, j), at, a.grid.span);
         wxor(x[0], d[0]);
     }
     for (int r = 0; r < a.m; ++r) {
-        lh_update_load<W, 1>(d, lh_verify_rec<PTR>(a, s, r), at, a.span);
+        lh_update_load<W, 1>(d, lh_verify_rec<PTR>(a, s, r), at, a.grid.span);
         uint32_t any = 0;
 #pragma unroll
         for (int w = 0; w < Word<W>::N; ++w) any |= d[0].v[w] ^ x[0].v[w];
@@ -583,18 +601,12 @@ __device__ __forceinline__ void lh_verify_flat(const lh::VerifyArgs &a, long lon
 template <bool PTR>
 __global__ void __launch_bounds__(256) lh_verify_kernel(lh::VerifyArgs a) {
     constexpr int TO = lh::kGenericTileOut;
-    long long chunk = blockIdx.x;
-    int tile = 0;
-    if (a.tiles > 1) {  // workgroups b, b + 8, ...: the tiles of chunk (b / (8 tiles)) * 8 + b % 8
-        const long long q = chunk >> 3;
-        tile = (int)(q % a.tiles);
-        chunk = (q / a.tiles) * 8 + (chunk & 7);
-    }
-    const long long t = chunk * 256 + threadIdx.x;
-    const long long s = t / a.nch;
+    int tile;
+    const long long t = lh_chunk_of(a.grid, tile) * 256 + threadIdx.x;
+    const long long s = t / a.grid.nch;
     if (s >= a.stripes) return;
-    const int c = (int)(t - s * a.nch);
-    if (a.flat) {
+    const int c = (int)(t - s * a.grid.nch);
+    if (a.grid.flat) {
         lh_verify_flat<PTR>(a, s, c);
         return;
     }
@@ -638,18 +650,18 @@ __device__ __forceinline__ void lh_syndromes(const lh::VerifyArgs &a, long long 
     constexpr int TO = lh::kGenericTileOut;
 #pragma unroll
     for (int i = 0; i < TO; ++i)
-        if (i < ni) lh_update_load<W, 8>(acc[i], lh_verify_rec<PTR>(a, s, i0 + i), at, a.span);
+        if (i < ni) lh_update_load<W, 8>(acc[i], lh_verify_rec<PTR>(a, s, i0 + i), at, a.grid.span);
     const uint8_t *g = a.G + (long long)i0 * a.k;
     Word<W> cur[8];
     uint32_t e[TO];
-    lh_update_load<W, 8>(cur, lh_verify_data<PTR>(a, s, 0), at, a.span);
+    lh_update_load<W, 8>(cur, lh_verify_data<PTR>(a, s, 0), at, a.grid.span);
 #pragma unroll
     for (int i = 0; i < TO; ++i) e[i] = i < ni ? g[i * a.k] : 0;
     for (int j = 0; j < a.k; ++j) {
         const int jn = j + 1 < a.k ? j + 1 : j;  // (the last column reloads itself)
         Word<W> nxt[8];
         uint32_t en[TO];
-        lh_update_load<W, 8>(nxt, lh_verify_data<PTR>(a, s, jn), at, a.span);
+        lh_update_load<W, 8>(nxt, lh_verify_data<PTR>(a, s, jn), at, a.grid.span);
 #pragma unroll
         for (int i = 0; i < TO; ++i) en[i] = i < ni ? g[i * a.k + jn] : 0;
         Word<W> v[15];
@@ -681,7 +693,7 @@ __device__ __forceinline__ uint32_t lh_any(const Word<W> (&d)[8]) {
 template <int W, bool PTR>
 __device__ __forceinline__ uint32_t lh_locate_lane(const lh::VerifyArgs &a, long long s, int c) {
     constexpr int TO = lh::kGenericTileOut;
-    const int at = min(c * W, max(a.span - W, 0));  // (the last lane's window ends with the span)
+    const int at = lh_lane_at<W>(a.grid.span, c);
     Word<W> acc[TO][8];
     int ni = min(TO, a.m);
     lh_syndromes<W, PTR>(a, s, at, 0, ni, acc);
@@ -728,13 +740,13 @@ __device__ __forceinline__ uint32_t lh_locate_lane(const lh::VerifyArgs &a, long
 template <bool PTR>
 __device__ __forceinline__ uint32_t lh_locate_flat(const lh::VerifyArgs &a, long long s, int c) {
     constexpr int W = 16;
-    const int at = min(c * W, max(a.span - W, 0));
+    const int at = lh_lane_at<W>(a.grid.span, c);
     Word<W> d[1], r[1], s0;
-    lh_update_load<W, 1>(d, lh_verify_data<PTR>(a, s, 0), at, a.span);
+    lh_update_load<W, 1>(d, lh_verify_data<PTR>(a, s, 0), at, a.grid.span);
     uint32_t some = 0, diff = 0;
     wzero(s0);
     for (int i = 0; i < a.m; ++i) {
-        lh_update_load<W, 1>(r, lh_verify_rec<PTR>(a, s, i), at, a.span);
+        lh_update_load<W, 1>(r, lh_verify_rec<PTR>(a, s, i), at, a.grid.span);
         wxor(r[0], d[0]);
         if (i == 0) s0 = r[0];
 #pragma unroll
@@ -753,13 +765,13 @@ template <bool PTR>
 __global__ void __launch_bounds__(256) lh_locate_kernel(lh::LocateArgs a) {
     const lh::VerifyArgs &v = a.v;
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long s = t / v.nch;
+    const long long s = t / v.grid.nch;
     if (s >= v.stripes) return;
-    const int c = (int)(t - s * v.nch);
+    const int c = (int)(t - s * v.grid.nch);
     const uint8_t *bad = v.bad_rows + s * v.m;
     for (int r = 0; r < v.m; ++r)
         if (!bad[r]) return;  // not every row is bad: the finishing kernel has the answer
-    const uint32_t vote = v.flat ? lh_locate_flat<PTR>(v, s, c) : lh_locate_lane<kUpdateLane, PTR>(v, s, c);
+    const uint32_t vote = v.grid.flat ? lh_locate_flat<PTR>(v, s, c) : lh_locate_lane<kUpdateLane, PTR>(v, s, c);
     if (!vote) return;
     uint32_t *word = a.votes + s;
     if (vote != lh::kLocateConflict) {
@@ -865,7 +877,7 @@ __global__ void __launch_bounds__(256) lh_reconstruct_coef_kernel(lh::Reconstruc
     // Erased originals, ascending (as the planner counts them): distinct rows leave as many as
     // there are recovery rows among the survivors, at most min(k, m) <= 127.
     int e = 0;
-    if (!bad && !a.flat) {
+    if (!bad && !a.grid.flat) {
         const unsigned long long below = (1ull << lane) - 1;
         for (int i0 = 0; i0 < k; i0 += 64) {
             const int i = i0 + lane;
@@ -879,8 +891,8 @@ __global__ void __launch_bounds__(256) lh_reconstruct_coef_kernel(lh::Reconstruc
             e += __builtin_popcountll(bm);
         }
     }
-    const lh::PlanView pv(a.plan + (live && !a.flat ? s : 0) * a.plan_stride, k, m, k < m ? k : m);
-    if (!bad && !a.flat && (pv.e() != e || pv.p[1] != 0)) bad = true;  // (the plan is of these rows)
+    const lh::PlanView pv(a.plan + (live && !a.grid.flat ? s : 0) * a.plan_stride, k, m, k < m ? k : m);
+    if (!bad && !a.grid.flat && (pv.e() != e || pv.p[1] != 0)) bad = true;  // (the plan is of these rows)
     if (live && lane == 0) {
         if (a.status) a.status[s] = bad ? -1 : 0;
         a.valid[s] = bad ? 0 : 1;
@@ -897,7 +909,7 @@ __global__ void __launch_bounds__(256) lh_reconstruct_coef_kernel(lh::Reconstruc
             const int at = slot_of[w];
             if (at != 0xFF) {
                 v = slot == at;
-            } else if (a.flat) {
+            } else if (a.grid.flat) {
                 v = 1;
             } else if (w < k) {
                 v = W[eidx[w] * k + slot];
@@ -920,7 +932,7 @@ __global__ void __launch_bounds__(256) lh_reconstruct_coef_kernel(lh::Reconstruc
 template <int W, int NS, bool PTR, bool UNI>
 __device__ __forceinline__ void lh_reconstruct_lane(const lh::ReconstructArgs &a, long long s, int c, int i0, int ni) {
     constexpr int TO = lh::kGenericTileOut;
-    const int at = min(c * W, max(a.span - W, 0));  // (the last lane's window ends with the span)
+    const int at = lh_lane_at<W>(a.grid.span, c);
     const uint8_t *wr = a.want_rows + s * a.want + i0;
     bool on[TO], any = false;
 #pragma unroll
@@ -940,14 +952,14 @@ __device__ __forceinline__ void lh_reconstruct_lane(const lh::ReconstructArgs &a
         for (int y = 0; y < NS; ++y) wzero(acc[i][y]);
     Word<W> cur[NS];
     uint32_t e[TO];
-    lh_update_load<W, NS>(cur, slot(0), at, a.span);
+    lh_update_load<W, NS>(cur, slot(0), at, a.grid.span);
 #pragma unroll
     for (int i = 0; i < TO; ++i) e[i] = on[i] ? cf[i * a.k] : 0;
     for (int j = 0; j < a.k; ++j) {
         const int jn = j + 1 < a.k ? j + 1 : j;  // (the last column reloads itself)
         Word<W> nxt[NS];
         uint32_t en[TO];
-        lh_update_load<W, NS>(nxt, slot(jn), at, a.span);
+        lh_update_load<W, NS>(nxt, slot(jn), at, a.grid.span);
 #pragma unroll
         for (int i = 0; i < TO; ++i) en[i] = on[i] ? cf[i * a.k + jn] : 0;
         if constexpr (NS == 8) {
@@ -973,7 +985,7 @@ __device__ __forceinline__ void lh_reconstruct_lane(const lh::ReconstructArgs &a
     for (int i = 0; i < TO; ++i) {
         if (on[i]) {
             uint8_t *out = PTR ? a.out_ptrs[s * a.want + i0 + i] : a.out + s * a.out_stride + (long long)(i0 + i) * a.bytes;
-            lh_update_store<W, NS>(out, acc[i], c, a.span);
+            lh_update_store<W, NS>(out, acc[i], c, a.grid.span);
         }
     }
 }
@@ -983,22 +995,16 @@ __device__ __forceinline__ void lh_reconstruct_lane(const lh::ReconstructArgs &a
 template <bool PTR>
 __global__ void __launch_bounds__(256) lh_reconstruct_kernel(lh::ReconstructArgs a) {
     constexpr int TO = lh::kGenericTileOut;
-    long long chunk = blockIdx.x;
-    int tile = 0;
-    if (a.tiles > 1) {  // workgroups b, b + 8, ...: the tiles of chunk (b / (8 tiles)) * 8 + b % 8
-        const long long q = chunk >> 3;
-        tile = (int)(q % a.tiles);
-        chunk = (q / a.tiles) * 8 + (chunk & 7);
-    }
-    const long long t = chunk * 256 + threadIdx.x;
-    const long long s = t / a.nch;
+    int tile;
+    const long long t = lh_chunk_of(a.grid, tile) * 256 + threadIdx.x;
+    const long long s = t / a.grid.nch;
     if (s >= a.stripes) return;
-    const int c = (int)(t - s * a.nch);
+    const int c = (int)(t - s * a.grid.nch);
     if (!a.valid[s]) return;
-    for (int i0 = tile * TO; i0 < a.want; i0 += a.tiles * TO) {
+    for (int i0 = tile * TO; i0 < a.want; i0 += a.grid.tiles * TO) {
         const int ni = min(TO, a.want - i0);
-        if (a.flat) lh_reconstruct_lane<16, 1, PTR, false>(a, s, c, i0, ni);
-        else if (a.nch % 64 == 0) lh_reconstruct_lane<kUpdateLane, 8, PTR, true>(a, s, c, i0, ni);  // whole waves per stripe
+        if (a.grid.flat) lh_reconstruct_lane<16, 1, PTR, false>(a, s, c, i0, ni);
+        else if (a.grid.nch % 64 == 0) lh_reconstruct_lane<kUpdateLane, 8, PTR, true>(a, s, c, i0, ni);  // whole waves per stripe
         else lh_reconstruct_lane<kUpdateLane, 8, PTR, false>(a, s, c, i0, ni);
     }
 }
@@ -2343,33 +2349,52 @@ hipError_t launch_update(const UpdateArgs &a, hipStream_t st) {
     return hipGetLastError();
 }
 
-hipError_t launch_verify(const VerifyArgs &a, hipStream_t st) {
-    if (a.k < 1 || a.m < 1 || a.bytes < 1 || (!a.flat && a.bytes % 8 != 0) || (!a.status && !a.bad_rows) || !a.zero)
-        return hipErrorInvalidValue;
-    VerifyArgs g = a;
-    g.span = a.flat ? a.bytes : a.bytes / 8;
-    const int lane = a.flat ? 16 : kUpdateLane;
-    g.nch = (g.span + lane - 1) / lane;
-    const long long lanes = (long long)a.stripes * g.nch;
-    if (lanes <= 0) return hipSuccess;
-    long long groups = (lanes + 255) / 256;
-    g.tiles = a.flat ? 1 : (a.m + kGenericTileOut - 1) / kGenericTileOut;
+// The workgroups of 256 lanes of a lane grid: with row tiles, whole groups of 8 chunks times the tiles.
+static long long grid_groups(const LaneGrid &g, int stripes) {
+    long long groups = ((long long)stripes * g.nch + 255) / 256;
     if (g.tiles > 1) groups = (groups + 7) / 8 * 8 * g.tiles;
-    if (groups > 0x7FFFFFFF) return hipErrorInvalidValue;
+    return groups;
+}
+
+// Fills the lane grid (the lanes: lh_update_kernel) from the block size, `flat` and the rows tiled
+// on the grid (0: none; flat loops over them).  Returns its workgroups: 0 without stripes, -1 for a
+// block the lanes cannot take or more than 2^31 - 1 workgroups (the host has refused both).
+static long long lane_grid(LaneGrid &g, int bytes, int flat, int rows, int stripes) {
+    if (bytes < 1 || (!flat && bytes % 8 != 0)) return -1;
+    g.flat = flat;
+    g.span = flat ? bytes : bytes / 8;
+    const int lane = flat ? 16 : kUpdateLane;
+    g.nch = (g.span + lane - 1) / lane;
+    g.tiles = flat || rows < 1 ? 1 : (rows + kGenericTileOut - 1) / kGenericTileOut;
+    if (stripes <= 0) return 0;
+    const long long groups = grid_groups(g, stripes);
+    return groups > 0x7FFFFFFF ? -1 : groups;
+}
+
+// launch_verify on a block of the caller's, which keeps the grid it fills in (launch_locate).
+static hipError_t enqueue_verify(VerifyArgs &g, hipStream_t st) {
+    if (g.k < 1 || g.m < 1 || (!g.status && !g.bad_rows) || !g.zero) return hipErrorInvalidValue;
+    const long long groups = lane_grid(g.grid, g.bytes, g.grid.flat, g.m, g.stripes);
+    if (groups <= 0) return groups ? hipErrorInvalidValue : hipSuccess;
     // The kernel stores only the 1s: both outputs start from zero, by device-to-device copies
     // from the zero page in front of the kernel on the same stream (copy nodes under capture).
     // Not hipMemsetAsync: captured, its node zeroes on the first replay and on later ones writes
     // stray bytes into the destination for some sizes (24 and 96 bytes among them, ROCm 7.2);
     // copy nodes of every size tried replay correctly.
     hipError_t e = hipSuccess;
-    if (a.status) e = hipMemcpyAsync(a.status, a.zero, (size_t)a.stripes, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess && a.bad_rows)
-        e = hipMemcpyAsync(a.bad_rows, a.zero, (size_t)a.stripes * a.m, hipMemcpyDeviceToDevice, st);
+    if (g.status) e = hipMemcpyAsync(g.status, g.zero, (size_t)g.stripes, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && g.bad_rows)
+        e = hipMemcpyAsync(g.bad_rows, g.zero, (size_t)g.stripes * g.m, hipMemcpyDeviceToDevice, st);
     if (e != hipSuccess) return e;
-    const bool ptr = a.table != 0;
+    const bool ptr = g.table != 0;
     hipLaunchKernelGGL(ptr ? lh_verify_kernel<true> : lh_verify_kernel<false>, dim3((unsigned)groups), dim3(256), 0, st, g);
     note_launch(ptr ? "lh_verify_kernel(pointer table)" : "lh_verify_kernel");
     return hipGetLastError();
+}
+
+hipError_t launch_verify(const VerifyArgs &a, hipStream_t st) {
+    VerifyArgs g = a;
+    return enqueue_verify(g, st);
 }
 
 hipError_t launch_locate(const LocateArgs &a, hipStream_t st) {
@@ -2377,19 +2402,17 @@ hipError_t launch_locate(const LocateArgs &a, hipStream_t st) {
         (a.v.m >= 2 && a.v.k + a.v.m > 255))
         return hipErrorInvalidValue;
     if (a.v.stripes <= 0) return hipSuccess;
-    hipError_t e = launch_verify(a.v, st);  // (checks the rest of the shape; clears bad_rows first)
-    if (e != hipSuccess) return e;
     LocateArgs g = a;
-    g.v.span = a.v.flat ? a.v.bytes : a.v.bytes / 8;
-    g.v.nch = (g.v.span + (a.v.flat ? 16 : kUpdateLane) - 1) / (a.v.flat ? 16 : kUpdateLane);
-    g.v.tiles = 1;
+    hipError_t e = enqueue_verify(g.v, st);  // (checks the rest of the shape; clears bad_rows first)
+    if (e != hipSuccess) return e;
+    g.v.grid.tiles = 1;  // the scrub's lanes on one plain grid: no more workgroups than the scrub's, which are in range
     const bool ptr = a.v.table != 0;
     if (a.v.m >= 2) {  // (m == 1: nothing to search, the finishing kernel does not read the votes)
-        const long long groups = ((long long)a.v.stripes * g.v.nch + 255) / 256;  // (launch_verify checked the range)
         // the votes start from zero by a copy from the zero page, as launch_verify clears its outputs
         e = hipMemcpyAsync(a.votes, a.v.zero, (size_t)a.v.stripes * sizeof(uint32_t), hipMemcpyDeviceToDevice, st);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(ptr ? lh_locate_kernel<true> : lh_locate_kernel<false>, dim3((unsigned)groups), dim3(256), 0, st, g);
+        hipLaunchKernelGGL(ptr ? lh_locate_kernel<true> : lh_locate_kernel<false>,
+                           dim3((unsigned)grid_groups(g.v.grid, a.v.stripes)), dim3(256), 0, st, g);
         note_launch(ptr ? "lh_locate_kernel(pointer table)" : "lh_locate_kernel");
         e = hipGetLastError();
         if (e != hipSuccess) return e;
@@ -2400,22 +2423,14 @@ hipError_t launch_locate(const LocateArgs &a, hipStream_t st) {
 }
 
 hipError_t launch_reconstruct(const ReconstructArgs &a, hipStream_t st) {
-    if (a.k < 1 || a.m < 1 || a.k + a.m > 255 || a.want < 1 || (long long)a.want * a.k > 0x7FFFFFFF || a.bytes < 1 ||
-        (!a.flat && a.bytes % 8 != 0) ||
-        !a.coef || !a.valid || (!a.flat && !a.plan))
+    if (a.k < 1 || a.m < 1 || a.k + a.m > 255 || a.want < 1 || (long long)a.want * a.k > 0x7FFFFFFF || !a.coef ||
+        !a.valid || (!a.grid.flat && !a.plan))
         return hipErrorInvalidValue;
-    if (a.stripes <= 0) return hipSuccess;
     ReconstructArgs g = a;
-    g.span = a.flat ? a.bytes : a.bytes / 8;
-    const int lane = a.flat ? 16 : kUpdateLane;
-    g.nch = (g.span + lane - 1) / lane;
-    const long long lanes = (long long)a.stripes * g.nch;
-    long long groups = (lanes + 255) / 256;
     // the wanted-row tiles on the grid, as launch_verify places its row tiles: 18.5 against 20.5 ms
     // looped in the lane at k128/m32/8192 x 8 192, want 32 (profiles/reconstruct_variants.txt)
-    g.tiles = a.flat ? 1 : (a.want + kGenericTileOut - 1) / kGenericTileOut;
-    if (g.tiles > 1) groups = (groups + 7) / 8 * 8 * g.tiles;
-    if (groups > 0x7FFFFFFF) return hipErrorInvalidValue;
+    const long long groups = lane_grid(g.grid, a.bytes, a.grid.flat, a.want, a.stripes);
+    if (groups <= 0) return groups ? hipErrorInvalidValue : hipSuccess;
     hipLaunchKernelGGL(lh_reconstruct_coef_kernel, dim3((unsigned)((a.stripes + 3) / 4)), dim3(256), 0, st, g);
     note_launch("lh_reconstruct_coef_kernel");
     hipError_t e = hipGetLastError();

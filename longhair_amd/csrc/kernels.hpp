@@ -209,6 +209,18 @@ struct UpdateArgs {
                                   // sub-block, or the whole block when flat) and lanes per stripe
 };
 
+// Which lane owns which bytes in the scrub, locate and repair kernels: derived by the launcher
+// (lane_grid in kernels.hip, which sets all but `flat`), read by the kernel (lh_chunk_of,
+// lh_lane_at).  The lanes are lh_update_kernel's, the tiles lh_verify_kernel's; see there.
+struct LaneGrid {
+    int flat;                     // m == 1 or k == 1 (set by the caller): every coefficient is 0 or 1,
+                                  // 16-byte lanes over the block's bytes, any block size
+    int span;                     // bytes a lane column runs over: bytes / 8 of each sub-block, or the
+                                  // whole block when flat
+    int nch;                      // lanes per stripe
+    int tiles;                    // row tiles on the grid (1: none)
+};
+
 // Recovery scrub (cauchy_256_verify_batch, lh_verify_kernel): row r of stripe s is bad iff
 // recovery_r ^ sum_j B(G[r][j]) data_j != 0 over all k data blocks.  Reads only; stores the byte 1
 // to bad_rows[s*m + r] and status[s] of a bad row (launch_verify zeroes both outputs first).
@@ -227,8 +239,7 @@ struct VerifyArgs {
     const uint8_t *zero;          // device zeros, at least stripes * m bytes (stripes without bad_rows)
     const uint8_t *G;             // m x k generator (row 0 = ones); unused when `flat`
     int k, m, bytes, stripes;
-    int flat;                     // m == 1 or k == 1: every coefficient is 1, lanes over the block's bytes
-    int span, nch, tiles;        // set by launch_verify: as UpdateArgs, and the row tiles of the grid
+    LaneGrid grid;                // tiles: the row tiles
 };
 
 // Locate (cauchy_256_locate_batch): the scrub of `v` into the workspace's bad_rows (v.status NULL,
@@ -240,7 +251,7 @@ struct VerifyArgs {
 // kLocateConflict two lanes disagreed or one found no column.
 constexpr uint32_t kLocateConflict = 0xFFFFFFFFu;
 struct LocateArgs {
-    VerifyArgs v;                 // data, recovery, G, shape and lanes (span, nch) as the scrub's
+    VerifyArgs v;                 // data, recovery, G, shape and the scrub's lane grid (launch_locate: tiles 1)
     uint32_t *votes;              // workspace, stripes words
     int8_t *status;               // stripes: 0 clean, 1 rows[s] is the corrupt block, 2 no single block
     uint8_t *rows;                // stripes: the row (data x, recovery k + r), else 0xFF
@@ -273,8 +284,7 @@ struct ReconstructArgs {
     const uint8_t *gf_exp;        // 512
     const int16_t *gf_log;        // 256
     int k, m, want, bytes, stripes;
-    int flat;                     // m == 1 or k == 1: every coefficient is 0 or 1, lanes over the block's bytes
-    int span, nch, tiles;         // set by launch_reconstruct: as UpdateArgs, and the wanted-row tiles of the grid
+    LaneGrid grid;                // tiles: the wanted-row tiles
 };
 
 // Launch trace (codec.cpp): every launch site records the kernel it enqueued, so the
